@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Poisson-learning sweep rate on the MNIST-shaped k=10 graph (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1], SURVEY.md section 8d "Config 2"): n = 70000 vertices,
 real MNIST label vector (tests/golden/MNIST_labels.npz), synthetic d = 20 Gaussian-blob
@@ -12,6 +12,10 @@ stop test fires (T = 50 sweeps on this graph), all on the device, inputs residen
 value = sweeps per second (Poisson iters/sec); edges*classes/sec = value * nnz * C is reported
 beside it.  N > 1: every rank owns 70000 vertices of an (N*70000)-vertex graph (weak scaling),
 vertex-partitioned after an RCM reordering, one RCCL halo exchange per sweep.
+A plain one-GPU run builds the graph once, warms up, times exactly --steps fp64 steps and prints the line.  --full adds
+everything beside the headline: the fp32 sweep, the oracle parity check, the CPU baselines, repeated graph builds and
+fresh fits, the rocprofv3 traffic passes, the configs block and the 10^6-vertex shard line.  --dump-outputs DIR writes
+what the last timed step computed (u.npy: the n x C iterate, T.npy: its sweep count, both float64).
 """
 import os
 import sys
@@ -678,6 +682,13 @@ def traffic_child():
         model.fit(train_ind, labels[train_ind])
 
 
+def dump_outputs(directory, **arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy in float64 (the config-2 iterate is 5.6 MB)."""
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + '.npy'), np.asarray(a, dtype=np.float64))
+
+
 def run_single(args):
     import graphlearning_amd as gl
     from graphlearning_amd import _hip, _build
@@ -686,37 +697,40 @@ def run_single(args):
     labels = load_labels(N_PER_RANK)
     X = make_features(labels)
     gl.weightmatrix.knn(X[:4096], K_NN)            # library start-up (HIP context, code objects) is not graph-build time
-    # the graph is built four times: the FIRST call at this size also allocates the page-locked result arrays and the device
-    # work buffers of its size class (reported as first_call_s); later builds recycle them -- the steady state a user who builds
-    # graph after graph sees (knn_plus_weights_s = the fastest of the three)
-    build_s = []
-    for _ in range(4):
-        t0 = time.perf_counter()
-        W = gl.weightmatrix.knn(X, K_NN)
-        build_s.append(time.perf_counter() - t0)
-    t_graph_first, t_graph = build_s[0], min(build_s[1:])
-    knn_stats = _hip.knn_stats()
     train_ind = gl.trainsets.generate(labels, rate=1, seed=0)
     train_labels = labels[train_ind]
-    # first use of a NEW graph: a fresh matrix, a fresh model, its first fit_predict (operator upload, plan, launch-graph capture,
-    # T sweeps, label decision), host arrays in and numpy out -- against `ms_per_step`, which is the sweeps alone
-    fresh_ms = []
-    for _ in range(4):
-        Wf = gl.weightmatrix.knn(X, K_NN)
-        t0 = time.perf_counter()
-        mf = gl.ssl.poisson(Wf, solver='gradient_descent')
-        mf.fit_predict(train_ind, train_labels)
-        fresh_ms.append((time.perf_counter() - t0) * 1e3)
-        del mf                                   # (the model's teardown -- launch graph, plan, buffers: ~1 ms -- is not part of a first use)
-    del Wf
+    if args.full:
+        # the graph is built four times: the FIRST call at this size also allocates the page-locked result arrays and the device
+        # work buffers of its size class (reported as first_call_s); later builds recycle them -- the steady state a user who builds
+        # graph after graph sees (knn_plus_weights_s = the fastest of the three)
+        build_s = []
+        for _ in range(4):
+            t0 = time.perf_counter()
+            W = gl.weightmatrix.knn(X, K_NN)
+            build_s.append(time.perf_counter() - t0)
+        t_graph_first, t_graph = build_s[0], min(build_s[1:])
+        knn_stats = _hip.knn_stats()
+        # first use of a NEW graph: a fresh matrix, a fresh model, its first fit_predict (operator upload, plan, launch-graph capture,
+        # T sweeps, label decision), host arrays in and numpy out -- against `ms_per_step`, which is the sweeps alone
+        fresh_ms = []
+        for _ in range(4):
+            Wf = gl.weightmatrix.knn(X, K_NN)
+            t0 = time.perf_counter()
+            mf = gl.ssl.poisson(Wf, solver='gradient_descent')
+            mf.fit_predict(train_ind, train_labels)
+            fresh_ms.append((time.perf_counter() - t0) * 1e3)
+            del mf                                   # (the model's teardown -- launch graph, plan, buffers: ~1 ms -- is not part of a first use)
+        del Wf
+    else:
+        W = gl.weightmatrix.knn(X, K_NN)
     n, nnz, C = W.shape[0], W.nnz, N_CLASSES
 
-    # the timed region: batches of EXACTLY --steps steps, each bracketed by synchronisation; batches are repeated until
-    # >= MIN_TIMED_S of sweeps have been timed (a 20-step batch is 13 ms: one noisy batch must not move the headline);
-    # the reported batch is the MEDIAN one, min / max beside it
+    # the timed region: batches of EXACTLY --steps steps, each bracketed by synchronisation; by default ONE batch (the line's
+    # `steps` are the steps timed).  --min-timed-s S repeats the batches until S seconds of sweeps have been timed and reports
+    # the MEDIAN one, min / max beside it
     MIN_TIMED_S = float(args.min_timed_s)
     results = {}
-    for dtype in (np.float64, np.float32):
+    for dtype in ((np.float64, np.float32) if args.full else (np.float64,)):
         model = gl.ssl.poisson(W, solver='gradient_descent', use_cuda=(dtype == np.float32))
         dev, aux = model._operators()
         source, k = gl.ssl._poisson_source(n, train_ind, train_labels)
@@ -731,7 +745,7 @@ def run_single(args):
         batches = []
         T = 0
         total = 0.0
-        while total < MIN_TIMED_S or len(batches) < 5:
+        while not batches or total < MIN_TIMED_S:
             device_sync()
             dev_ms = 0.0
             l0 = sweep.launches()
@@ -753,15 +767,19 @@ def run_single(args):
                               timed_total_s=total)
         sweep.close()
 
-    r64, r32 = results[np.float64], results[np.float32]
+    r64 = results[np.float64]
     T = r64['T']
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, u=r64['u'], T=np.array([T]))
     sweeps = args.steps * T
     value = sweeps / r64['wall']
     # dominant kernel: spmm_sell_kernel<double,4,true,false>; HIP events bracket the launches on the library's stream
     abytes = algorithmic_bytes(n, nnz, C, 8, 8)
     avg_launch_s = r64['dev_ms'] * 1e-3 / max(r64['launches'], 1)
     achieved = abytes / avg_launch_s / 1e9
-    if args.no_traffic:
+    if not args.full:
+        traffic, traffic_source = None, 'not measured (--full)'
+    elif args.no_traffic:
         traffic, traffic_source = None, 'skipped (--no-traffic)'
     else:
         traffic, traffic_source = measure_traffic()
@@ -775,8 +793,6 @@ def run_single(args):
                      'the records come from HBM / Infinity Cache; there the bound is the random-line gather rate of the memory '
                      'system (54 G lines/s = 6.9 TB/s of 128-byte lines measured by scripts/probes/gather_probe.hip, '
                      'profiles/r02_gather_probe.txt), reached to ~85-115 %, which caps the algorithmic fraction near 0.2.')
-    cpu, parity, T_ref = cpu_baseline(W, train_ind, train_labels, r64['u'], T)
-    a32 = algorithmic_bytes(n, nnz, C, 4, 4)
     line = {
         'metric': 'Poisson iters/sec', 'value': value, 'unit': 'iters/s', 'n_gpus': 1, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': r64['wall'] / args.steps * 1e3, 'higher_is_better': True,
@@ -790,23 +806,29 @@ def run_single(args):
                    'timed_total_s': r64['timed_total_s']},
         'edges_classes_per_sec': value * nnz * C,
         'roofline': roof,
-        'cpu_baseline': cpu,
-        'cpu_baseline_all_cores': cpu_baseline_omp(W, train_ind, train_labels),
-        'speedup_vs_cpu_baseline': value / cpu['value'],
-        'parity': {'bit_identical_to_oracle': parity, 'T': T, 'T_oracle': T_ref,
-                   'fp32_max_abs_diff': float(np.max(np.abs(r32['u'].astype(np.float64) - r64['u'])))},
-        'fp32': {'value': args.steps * r32['T'] / r32['wall'],
-                 'roofline_frac': a32 / (r32['dev_ms'] * 1e-3 / max(r32['launches'], 1)) / 1e9 / HBM_PEAK_GBS},
-        'graph_build': {'knn_plus_weights_s': t_graph, 'first_call_s': t_graph_first, 'all_calls_s': build_s,
-                        'fresh_fit_predict_ms': sorted(fresh_ms[1:])[1], 'fresh_fit_predict_all_ms': fresh_ms,
-                        'knn_tile_ms': knn_stats['tile_ms'], 'knn_filter': knn_stats['filter'],
-                        'knn_total_ms': knn_stats['total_ms'], 'fallback_rows': knn_stats['fallback_rows'],
-                        'sell': r64['info']},
     }
-    if not args.no_configs:
-        line['configs'] = other_configs(W, labels, train_ind, device_sync, knn_stats, X)
-    if not args.no_scale:
-        line['scale_shard_1e6'] = scale_shard_line(traffic=not args.no_traffic)
+    if args.full:
+        r32 = results[np.float32]
+        cpu, parity, T_ref = cpu_baseline(W, train_ind, train_labels, r64['u'], T)
+        a32 = algorithmic_bytes(n, nnz, C, 4, 4)
+        line.update({
+            'cpu_baseline': cpu,
+            'cpu_baseline_all_cores': cpu_baseline_omp(W, train_ind, train_labels),
+            'speedup_vs_cpu_baseline': value / cpu['value'],
+            'parity': {'bit_identical_to_oracle': parity, 'T': T, 'T_oracle': T_ref,
+                       'fp32_max_abs_diff': float(np.max(np.abs(r32['u'].astype(np.float64) - r64['u'])))},
+            'fp32': {'value': args.steps * r32['T'] / r32['wall'],
+                     'roofline_frac': a32 / (r32['dev_ms'] * 1e-3 / max(r32['launches'], 1)) / 1e9 / HBM_PEAK_GBS},
+            'graph_build': {'knn_plus_weights_s': t_graph, 'first_call_s': t_graph_first, 'all_calls_s': build_s,
+                            'fresh_fit_predict_ms': sorted(fresh_ms[1:])[1], 'fresh_fit_predict_all_ms': fresh_ms,
+                            'knn_tile_ms': knn_stats['tile_ms'], 'knn_filter': knn_stats['filter'],
+                            'knn_total_ms': knn_stats['total_ms'], 'fallback_rows': knn_stats['fallback_rows'],
+                            'sell': r64['info']},
+        })
+        if not args.no_configs:
+            line['configs'] = other_configs(W, labels, train_ind, device_sync, knn_stats, X)
+        if not args.no_scale:
+            line['scale_shard_1e6'] = scale_shard_line(traffic=not args.no_traffic)
     print(json.dumps(line))
 
 
@@ -965,12 +987,17 @@ def main():
     ap.add_argument('--workload', default='blobs', choices=['blobs', 'connected'],
                     help='multi-GPU config 2: the headline features (10 separate clusters) or the same with centre scale 0.8 '
                          '(one connected component: the halo exchange carries real rows)')
-    ap.add_argument('--no-traffic', action='store_true', help='skip the rocprofv3 counter passes (roofline.traffic = null)')
-    ap.add_argument('--no-scale', action='store_true', help='skip the n = 10^6 shard-size line')
-    ap.add_argument('--no-configs', action='store_true', help='skip the configs block (configs 3 and 5, Poisson CG, weightmatrix.knn)')
-    ap.add_argument('--min-timed-s', type=float, default=0.5,
-                    help='batches of --steps steps are repeated until this many seconds have been timed (at least 5 batches).  Profiling runs '
-                         'pass 0: rocprofv3 of ROCm 7.2 segfaults after 16 384 dispatches launched from device graphs (profiles/README.md)')
+    ap.add_argument('--full', action='store_true',
+                    help='one GPU: measure and check everything beside the headline (fp32 sweep, oracle parity, CPU baselines, graph builds and '
+                         'fresh fits, rocprofv3 traffic passes, the configs block, the 10^6-vertex shard line); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='one GPU: write what the last timed step computed to DIR/<name>.npy (u: the n x C iterate, T: its sweep count; float64)')
+    ap.add_argument('--no-traffic', action='store_true', help='--full: skip the rocprofv3 counter passes (roofline.traffic = null)')
+    ap.add_argument('--no-scale', action='store_true', help='--full: skip the n = 10^6 shard-size line')
+    ap.add_argument('--no-configs', action='store_true', help='--full: skip the configs block (configs 3 and 5, Poisson CG, weightmatrix.knn)')
+    ap.add_argument('--min-timed-s', type=float, default=0.0,
+                    help='one GPU: batches of --steps steps are repeated until this many seconds have been timed and the median batch is '
+                         'reported (default 0: one batch, exactly --steps timed steps)')
     ap.add_argument('--engine', default='glx', choices=['glx', 'torch'],
                     help='multi-GPU runs: the library-owned RCCL communicator with captured sweeps (default) or the torch.distributed engine')
     ap.add_argument('--force-dist', action='store_true', help='take the distributed path with one rank (tests)')
@@ -984,6 +1011,8 @@ def main():
     ap.add_argument('--dist-dry-run', action='store_true',
                     help='start the ranks, rendezvous over gloo, count them, print one line and stop: checks the launch path without a GPU')
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.config == 4 or args.dist_dry_run or args.force_dist):
+        ap.error('--dump-outputs is offered by the one-GPU config 2 line only')
     if args.traffic_child:
         traffic_child()
         return

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage: scripts/prof_groups.sh <tag> "<grp1 counters>" "<grp2 counters>" ...   (one rocprofv3 --pmc pass per group)
 tag=$1; shift
+root=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/grp_$tag
 mkdir -p $out
@@ -8,7 +9,7 @@ cd /tmp
 i=0
 for grp in "$@"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $out/g$i -o run -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 > $out/g$i.log 2>&1
+  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $out/g$i -o run -- python "$root/bench.py" --full --steps 3 --warmup 1 > $out/g$i.log 2>&1
   f=$(find $out/g$i -name "*counter_collection.csv" | head -1)
   python3 - "$f" <<'PY'
 import sys, csv, collections

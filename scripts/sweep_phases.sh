@@ -12,7 +12,7 @@ patch -p1 -s < scripts/probes/sweep_replay_experiment.patch || exit 1
 : > "$out/phases.txt"
 for v in 0 1 2 3 4 0; do
   GLX_CXXFLAGS=-DGLX_SWEEP_REPLAY=$v python -m graphlearning_amd._build > "$out/build$v.log" 2>&1 || { echo "build $v failed"; tail -5 "$out/build$v.log"; }
-  GLX_CXXFLAGS=-DGLX_SWEEP_REPLAY=$v python bench.py --steps 20 --warmup 5 --no-configs --no-scale --no-traffic > "$out/bench$v.json" 2> "$out/bench$v.err"
+  GLX_CXXFLAGS=-DGLX_SWEEP_REPLAY=$v python bench.py --full --steps 20 --warmup 5 --min-timed-s 0.5 --no-configs --no-scale --no-traffic > "$out/bench$v.json" 2> "$out/bench$v.err"
   python - "$out/bench$v.json" $v >> "$out/phases.txt" <<'PY'
 import json, sys
 names = {0: 'full kernel (shipped)', 1: 'gathers only (no bias load / store / stop reduction)', 2: 'stores only (header + epilogue, no chunk loop)',

@@ -308,6 +308,38 @@ def g9_plaplace():
     print('g9 done')
 
 
+def g12_lp_random():
+    """The reference's compiled lp_iterate_main (oracle/_ref/liblp_ref.so, as in g9) on the random operators of
+    tests/test_oracle_c.py::test_lp_iterate_restatement_equals_compiled_reference: inputs and the returned upper / lower
+    iterates, so that the test holds the restatement to them where the compiled reference is absent."""
+    import ctypes
+    ref = ctypes.CDLL(os.path.join(os.path.dirname(os.path.dirname(HERE)), 'oracle', '_ref', 'liblp_ref.so'))
+    f = getattr(ref, '_Z15lp_iterate_mainPdS_PiS0_S_S0_S_didbiii')
+    f.restype = None
+    vp = ctypes.c_void_p
+    rng = np.random.default_rng(1)
+    out = {}
+    for c, (n, dens, p, tol, T) in enumerate([(300, 0.03, 4.0, 1e-2, 5000), (800, 0.01, 20.0, 1e-1, 33), (150, 0.08, 2.2, 1e-6, 400)]):
+        A = sparse.random(n, n, density=dens, random_state=7, format='csr')
+        W = sparse.csr_matrix(A + A.T)
+        bdy = rng.permutation(n)[:n // 10]
+        val = rng.normal(size=len(bdy))
+        I, J, V = orc.ccode_arrays(W)
+        ru = np.max(val) * np.ones(n); rl = np.min(val) * np.ones(n); ru[bdy] = val; rl[bdy] = val
+        b32 = np.ascontiguousarray(bdy, dtype=np.int32)
+        f(ru.ctypes.data_as(vp), rl.ctypes.data_as(vp), J.ctypes.data_as(vp), I.ctypes.data_as(vp), V.ctypes.data_as(vp),
+          b32.ctypes.data_as(vp), val.ctypes.data_as(vp), ctypes.c_double(p), ctypes.c_int(T), ctypes.c_double(tol), ctypes.c_bool(False),
+          ctypes.c_int(n), ctypes.c_int(len(V)), ctypes.c_int(len(b32)))
+        out.update(csr_parts(W, 'c%d_W' % c))
+        out['c%d_bdy' % c] = bdy
+        out['c%d_val' % c] = val
+        out['c%d_params' % c] = np.array([p, tol, T], dtype=np.float64)
+        out['c%d_uu' % c] = ru
+        out['c%d_ul' % c] = rl
+    np.savez_compressed(os.path.join(HERE, 'g12_lp_random.npz'), **out)
+    print('g12 done')
+
+
 def g10_knn_cache():
     """f-2: the kNN cache file the reference's knnsearch(dataset=...) writes (weightmatrix.py:414-427) and the weight
     matrix its string path `knn('name', k)` (weightmatrix.py:126-127, 431-467) builds from it."""
@@ -520,5 +552,6 @@ if __name__ == '__main__':
     g9_plaplace()
     g10_knn_cache()
     g11_properly()
+    g12_lp_random()
     if args.large:
         g4_large()
