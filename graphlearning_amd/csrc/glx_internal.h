@@ -113,10 +113,10 @@ void glx_cg_ws_destroy(void* ws);
 // of its own (scripts/probes/graph_memset_probe.hip; found in round 6 when a poisoned pool turned a row of stop values into 1.4e306 on
 // the second replay of the stacked trials' head graph).  `p` 8-byte aligned, `bytes` a multiple of 8.
 int glx_zero_async(void* p, size_t bytes, hipStream_t st);
-// device work-buffer pool (graph.hip): size-class free lists in front of hipMalloc / hipFree
+// device work-buffer pool (memory.hip): size-class free lists in front of hipMalloc / hipFree
 int glx_pool_alloc(void** out, size_t bytes);
 void glx_pool_free(void* p);
-// small page-locked blocks (graph.hip): power-of-two classes in front of hipHostMalloc / hipHostFree (0.25 ms each)
+// small page-locked blocks (memory.hip): power-of-two classes in front of hipHostMalloc / hipHostFree (0.25 ms each)
 int glx_pinned_alloc(void** out, size_t bytes);
 void glx_pinned_free(void* p);
 
@@ -130,7 +130,7 @@ struct glx_knn_result {
   int32_t* order_dev = nullptr;     // ... or left on the device (rows reordered by the cellrank kernels): a pooled block of n entries
 };
 
-// a non-blocking stream and four events, handed out from a per-device list of idle sets and returned to it (graph.hip):
+// a non-blocking stream and four events, handed out from a per-device list of idle sets and returned to it (memory.hip):
 // creating and destroying them costs milliseconds -- as much as the kNN search of 70 000 points itself
 struct glx_work {
   hipStream_t stream = nullptr;
@@ -165,6 +165,12 @@ int glx_upload_sync(void* dst, const void* src, size_t bytes, const char* what);
 // in for its results) and below 128 KB: hipMemcpyAsync as before, complete when the caller synchronises `st`.
 int glx_download(void* dst_host, const void* src_dev, size_t bytes, hipStream_t st, const char* what);
 int glx_download_sync(void* dst_host, const void* src_dev, size_t bytes, const char* what);
+// `bytes` of device memory read back into page-locked memory (`back`, at least `bytes` of it, or null: a block of the call's own) and
+// compared word by word with the host array: how many 64-bit words differ, the first and last of them, and how many of them read zero
+struct GlxReadbackDiff { size_t bad = 0, first = 0, last = 0, zeros = 0; };
+int glx_compare_readback(const void* host, const void* dev, size_t bytes, GlxReadbackDiff* diff, unsigned long long* back = nullptr);
+// fn(t) for t in [0, nt) on the library's host worker threads and the caller; returns when all are done (memory.hip)
+void glx_host_parallel(int nt, const std::function<void(int)>& fn);
 #define GLX_UP(call) do { const int rc_up_ = (call); if (rc_up_) return rc_up_; } while (0)
 
 int glx_graph_plan(glx_graph* g, int G, SellPlan** out, bool relaxed = false);
@@ -384,7 +390,7 @@ int glx_project_device(glx_projector** pp, const void* dense_dev, int dtype, int
                        double* weights_inout, double* err_out, int* steps_out, int max_steps, int similarity, hipStream_t st,
                        const long long** d_labels_out, const std::function<int(bool)>* hook = nullptr);
 int glx_onehot_device(const long long* d_labels, void* dense_dev, int dtype, int64_t n, int C, hipStream_t st);
-int glx_project_scores(glx_projector** pp, int64_t n, int C, double** scores_out);
+int glx_project_scores(glx_projector** pp, int64_t n, int C, hipStream_t st, double** scores_out);
 int glx_onehot_records(const long long* d_labels, void* rec, int dtype, int64_t n, const RecLayout& L, const int32_t* perm, hipStream_t st);
 void glx_projector_destroy(glx_projector* p);
 

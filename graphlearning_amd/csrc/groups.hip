@@ -459,7 +459,7 @@ extern "C" int glx_sweep_groups_project(glx_sweep_groups* s, int b, const double
   int rc;
   if (dtype == GLX_F64) {
     double* scores = nullptr;
-    rc = glx_project_scores(&s->proj, s->n, s->C, &scores);
+    rc = glx_project_scores(&s->proj, s->n, s->C, s->stream, &scores);
     if (rc) return rc;
     prob = scores;
   }

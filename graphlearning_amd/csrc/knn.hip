@@ -11,6 +11,7 @@
 //   3. fallback -- rows that fail the check are redone by an exact fp64 scan.
 // This file: one pass of the search (knn_pass), the escalation to long lists, the C-ABI entry points.
 #include "knn_internal.h"
+#include <atomic>
 #include <chrono>
 #include <stdlib.h>
 #include <unistd.h>
@@ -39,12 +40,12 @@ extern "C" int glx_knn_set_options(const glx_knn_options* opt) {
 // kernel (i.e. through the L2s) -- and compared with the caller's array; differences are counted (glx_debug_counters) and described
 // on stderr.  Round 6: the one parity failure of the randomised soak that left evidence was a search whose device copy of ONE row of X
 // was not the caller's (EXPERIMENTS.md round 6, section 2).
-static int g_debug_flags = 0;
-static unsigned long long g_debug_counts[4] = {0, 0, 0, 0};   // uploads checked, uploads whose engine read-back differed, whose kernel read-back differed, bytes differing
+static std::atomic<int> g_debug_flags{0};
+static std::atomic<unsigned long long> g_debug_counts[4];   // uploads checked, uploads whose engine read-back differed, whose kernel read-back differed, bytes differing
 extern "C" int glx_debug_set(int flags) { g_debug_flags = flags; return GLX_OK; }
 extern "C" int glx_debug_counters(unsigned long long out[4]) {
   GLX_CHECK(out, GLX_EINVAL, "glx_debug_counters: null output");
-  for (int q = 0; q < 4; ++q) out[q] = g_debug_counts[q];
+  for (int q = 0; q < 4; ++q) out[q] = g_debug_counts[q].load();
   return GLX_OK;
 }
 __global__ __launch_bounds__(256) void knn_copy_u64_kernel(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, int64_t n) {
@@ -59,21 +60,21 @@ static int knn_verify_upload(const double* X_host, const double* X_dev, int64_t 
   struct Free { unsigned long long* p; ~Free() { hipHostFree(p); } } free_back{back};
   ++g_debug_counts[0];
   for (int pass = 0; pass < 2; ++pass) {
+    GlxReadbackDiff diff;
     if (pass == 0) {
-      GLX_HIP(hipMemcpy(back, X_dev, bytes, hipMemcpyDeviceToHost));
+      GLX_UP(glx_compare_readback(X_host, X_dev, bytes, &diff, back));
     } else {
       void* tmp = nullptr;
       GLX_HIP(hipMalloc(&tmp, bytes));                  // (a fresh allocation, not a pooled block)
       hipLaunchKernelGGL(knn_copy_u64_kernel, dim3(1024), dim3(256), 0, st, (const unsigned long long*)X_dev, (unsigned long long*)tmp, (int64_t)(bytes / 8));
       hipError_t e = hipStreamSynchronize(st);
-      if (e == hipSuccess) e = hipMemcpy(back, tmp, bytes, hipMemcpyDeviceToHost);
+      const int rc = e == hipSuccess ? glx_compare_readback(X_host, tmp, bytes, &diff, back) : GLX_OK;
       hipFree(tmp);
       GLX_HIP(e);
+      if (rc) return rc;
     }
     const unsigned long long* src = (const unsigned long long*)X_host;
-    size_t nbad = 0, first = 0, last = 0;
-    for (size_t i = 0; i < bytes / 8; ++i)
-      if (back[i] != src[i]) { if (!nbad) first = i; last = i; ++nbad; }
+    const size_t nbad = diff.bad, first = diff.first, last = diff.last;
     if (nbad) {
       ++g_debug_counts[1 + pass];
       g_debug_counts[3] += nbad * 8;
@@ -82,22 +83,19 @@ static int knn_verify_upload(const double* X_host, const double* X_dev, int64_t 
               pass == 0 ? "the copy engine" : "a kernel (through the L2s)", nbad, bytes / 8, first, last, first / d, last / d, (long long)n, d, first * 8, last * 8 + 7,
               (const void*)X_dev, (const void*)X_host);
       if (pass == 0) {
-        // what the wrong words hold: zeros, words of the SAME array from another place (a shifted or repeated piece), or nothing of it
-        size_t zeros = 0, shown = 0;
-        for (size_t i = first; i <= last; ++i) {
-          if (back[i] == src[i]) continue;
-          if (back[i] == 0) { ++zeros; continue; }
-          if (shown < 6) {
-            long long at = -1;
-            for (size_t j = 0; j < bytes / 8; ++j)
-              if (src[j] == back[i]) { at = (long long)j; break; }
-            fprintf(stderr, "[glx] knn DEBUG   word %zu: got %016llx (as a double %.6g), expected %016llx (%.6g); the value got %s%lld\n", i, back[i],
-                    __builtin_bit_cast(double, back[i]), src[i], __builtin_bit_cast(double, src[i]),
-                    at >= 0 ? "is word " : "occurs nowhere in the caller's array ", at);
-            ++shown;
-          }
+        // what the wrong words hold: words of the SAME array from another place (a shifted or repeated piece), or nothing of it
+        size_t shown = 0;
+        for (size_t i = first; i <= last && shown < 6; ++i) {
+          if (back[i] == src[i] || back[i] == 0) continue;
+          long long at = -1;
+          for (size_t j = 0; j < bytes / 8; ++j)
+            if (src[j] == back[i]) { at = (long long)j; break; }
+          fprintf(stderr, "[glx] knn DEBUG   word %zu: got %016llx (as a double %.6g), expected %016llx (%.6g); the value got %s%lld\n", i, back[i],
+                  __builtin_bit_cast(double, back[i]), src[i], __builtin_bit_cast(double, src[i]),
+                  at >= 0 ? "is word " : "occurs nowhere in the caller's array ", at);
+          ++shown;
         }
-        fprintf(stderr, "[glx] knn DEBUG   %zu of the wrong words are zero\n", zeros);
+        fprintf(stderr, "[glx] knn DEBUG   %zu of the wrong words are zero\n", diff.zeros);
       }
     }
   }

@@ -189,6 +189,7 @@ struct ProjBufs {
   float* stage32 = nullptr;       // float32 input of the one-shot entry point, before widening
   size_t stage_cap = 0;
   hipStream_t stream = nullptr;   // owned only by the one-shot entry point
+  hipStream_t used = nullptr;     // the stream the blocks serve (proj_alloc): release() drains it before they go back to the pools
   int64_t cap_n = 0;
   int cap_C = 0;
   double* w() const { return state; }
@@ -201,9 +202,9 @@ struct ProjBufs {
   double* mm() const { return state + 3 * cap_C + 4; }
   size_t image_words() const { return (size_t)3 * cap_C + 4; }
   void release() {
-    // (size-class pools of graph.hip: hipFree of the score block cost 0.23 ms per model, hipHostFree 0.25 -- the pools' contract is that
-    // nothing in flight uses a block handed back, which hipFree enforced by waiting for the device: wait for this object's stream)
-    if (stream) hipStreamSynchronize(stream);
+    // (size-class pools of memory.hip: hipFree of the score block cost 0.23 ms per model, hipHostFree 0.25 -- the pools' contract is that
+    // nothing in flight uses a block handed back, which hipFree enforced by waiting for the device: wait for the stream the blocks serve)
+    if (scores) hipStreamSynchronize(used);
     glx_pool_free(scores); glx_pool_free(bmin); glx_pool_free(bmax); glx_pool_free(state); glx_pool_free(labels); glx_pool_free(cnt_part);
     cnt_part = nullptr;
     if (ev) hipEventDestroy(ev);
@@ -227,10 +228,11 @@ static int proj_blocks(int64_t total) { return (int)std::min<int64_t>((total + 2
 static const int PROJ_ROW_BLOCKS = 2048;   // most workgroups of an argmax pass (sizes cnt_part)
 
 #define PJ_POOL(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-static int proj_alloc(ProjBufs& b, int64_t n, int C) {
+static int proj_alloc(ProjBufs& b, int64_t n, int C, hipStream_t st) {
   if (b.cap_n >= n && b.cap_C == C && b.scores) return GLX_OK;      // (the state block's layout depends on C)
   const int64_t keep_n = std::max<int64_t>(n, b.cap_n);
   b.release();
+  b.used = st;
   const int64_t total = keep_n * C;
   const int nb = proj_blocks(total);
   PJ_POOL(glx_pool_alloc((void**)&b.scores, total * 8));
@@ -375,7 +377,7 @@ static int argmax_project_any(const void* prob, int prob_dtype, int64_t n, int C
   }
   ProjBufs& b = *slot;
   hipStream_t st = b.stream;
-  int rc = proj_alloc(b, n, C);
+  int rc = proj_alloc(b, n, C, st);
   if (rc) return rc;
   if (prob_dtype == GLX_F32) {
     if (b.stage_cap < (size_t)n * C) {
@@ -418,11 +420,11 @@ __global__ __launch_bounds__(256) void onehot_kernel(const long long* __restrict
 
 // the projector's own fp64 (n, C) input array: a caller whose state is fp64 writes its prob straight into it and passes it as
 // `dense_dev` (no copy); anything else is widened / copied into it
-int glx_project_scores(glx_projector** pp, int64_t n, int C, double** scores_out) {
+int glx_project_scores(glx_projector** pp, int64_t n, int C, hipStream_t st, double** scores_out) {
   GLX_CHECK(pp && scores_out, GLX_EINVAL, "glx_project_scores: null argument");
   GLX_CHECK(C <= 4096, GLX_EUNSUPPORTED, "glx_sweep_project: C=%d too large", C);
   if (!*pp) *pp = new glx_projector();
-  int rc = proj_alloc((*pp)->b, n, C);
+  int rc = proj_alloc((*pp)->b, n, C, st);
   if (rc) return rc;
   *scores_out = (*pp)->b.scores;
   return GLX_OK;
@@ -436,7 +438,7 @@ int glx_project_device(glx_projector** pp, const void* dense_dev, int dtype, int
   GLX_CHECK(C <= 4096, GLX_EUNSUPPORTED, "glx_sweep_project: C=%d too large", C);
   if (!*pp) *pp = new glx_projector();
   ProjBufs& b = (*pp)->b;
-  int rc = proj_alloc(b, n, C);
+  int rc = proj_alloc(b, n, C, st);
   if (rc) return rc;
   const int64_t total = n * C;
   const unsigned grid = (unsigned)((total + 255) / 256);

@@ -96,7 +96,7 @@ extern "C" int glx_sweep_create(glx_graph* P, int C, int min_iter, int max_iter,
   if (rc) { delete s; return rc; }
   rc = glx_graph_plan(P, s->L.G, &s->plan);
   if (rc) { delete s; return rc; }
-// (work buffers from the size-class pool of graph.hip: a dozen hipMalloc / hipFree pairs per sweep object cost milliseconds)
+// (work buffers from the size-class pool of memory.hip: a dozen hipMalloc / hipFree pairs per sweep object cost milliseconds)
 #define SW_POOL(call) do { int rc_ = (call); if (rc_) { glx_sweep_destroy(s); return rc_; } } while (0)
 #define SW_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { glx_set_error("%s -> %s", #call, hipGetErrorString(e_)); glx_sweep_destroy(s); return GLX_EHIP; } } while (0)
   rc = glx_work_acquire(P->device, &s->work);
@@ -562,7 +562,7 @@ extern "C" int glx_sweep_project_iterate(glx_sweep* s, const double* priors, dou
   int rc;
   if (dtype == GLX_F64) {
     double* scores = nullptr;
-    rc = glx_project_scores(&s->proj, s->n_rows, s->C, &scores);
+    rc = glx_project_scores(&s->proj, s->n_rows, s->C, s->stream, &scores);
     if (rc) return rc;
     prob = scores;
   }
