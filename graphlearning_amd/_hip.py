@@ -1119,7 +1119,7 @@ class _KnnOptions(C.Structure):
 
 class knn_options:
     """Context manager: plan overrides for the calling thread's kNN searches (glx_knn_set_options) -- which candidate filter
-    ('bf16' | 'f32'), list length ('short' | 'long'), ref ranges per query block (1..8), operand form of the bf16 filter at
+    ('bf16' | 'f32'), list length ('short' | 'long'), ref ranges per query block (1..8; 1..32 for k > 60), operand form of the bf16 filter at
     d <= 21 (concat 0 | 1 | 2).  Every plan returns the same exact lists; tests and A/B measurements use this."""
 
     def __init__(self, filter=None, lists=None, nsplit=None, concat=None):
@@ -1153,7 +1153,7 @@ def _knn_cells(n, d, clustered, want_order):
 
 
 def knn_bruteforce(X, k, similarity='euclidean', device=None, query_range=None, cell_starts=None, clustered=None, want_order=False):
-    """Exact kNN (incl. self) on the GPU.  'angular' = euclidean on row-normalised data, formed
+    """Exact kNN (incl. self, k <= KNN_K_LISTS; KnnResult takes more) on the GPU.  'angular' = euclidean on row-normalised data, formed
     with the reference's own expression (weightmatrix.py:344-345).  cell_starts: the rows come in a coarse geometric
     order with cell c = rows [cell_starts[c], cell_starts[c+1]); the search skips the cells that cannot hold a
     neighbour (glx_knn_cells_range: the same lists, a fraction of the tiles on clustered data).  clustered: number of cells
@@ -1195,9 +1195,15 @@ _PINNED_CSR_MAX = 512 << 20      # above this the weight matrix comes back throu
 _KERNEL_ID = {'given': 0, 'uniform': 1, 'gaussian': 2, 'symgaussian': 3, 'distance': 4, 'singular': 5}
 
 
+KNN_K_LISTS = 60      # k (self included) of the list-returning searches: knn_bruteforce and the sharded build
+KNN_K_MAX = 1024      # k (self included) of KnnResult (glx_knn_search)
+
+
 class KnnResult:
     """A finished full search whose lists live on the device (glx_knn_search): `to_csr` builds the weight matrix from them
-    without a host round trip, `lists()` copies them out, `order()` is the cell order the search worked out (or None)."""
+    without a host round trip, `lists()` copies them out, `order()` is the cell order the search worked out (or None).
+    k (self included) from 1 to min(n, KNN_K_MAX); above KNN_K_LISTS the search takes its wide plan (longer and more
+    candidate lists, processed in chunks of queries), whose lists are the same exact lists."""
 
     def __init__(self, X, k, similarity='euclidean', device=None, clustered=None, want_order=False):
         X = _knn_input(X, similarity)
@@ -1351,4 +1357,5 @@ def knn_stats():
     check(load().glx_knn_stats(out), 'glx_knn_stats')
     return dict(tile_ms=out[0], rerank_ms=out[1], fallback_rows=out[2], total_ms=out[3], fallback_ms=out[4],
                 dpa=out[5], nsplit=out[6], KP=abs(out[7]), filter='bf16x3' if out[7] < 0 else 'f32', escalated_rows=out[8],
-                concatenated=int(out[9]), seed_sample=int(out[10]), visited_share=out[11], cells=int(out[12]))
+                concatenated=int(out[9]), seed_sample=int(out[10]), visited_share=out[11], cells=int(out[12]),
+                chunks=int(out[13]), wide=bool(out[14]), candidates=int(out[15]))

@@ -11,6 +11,7 @@
 //   3. fallback -- rows that fail the check are redone by an exact fp64 scan.
 // This file: one pass of the search (knn_pass), the escalation to long lists, the C-ABI entry points.
 #include "knn_internal.h"
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <stdlib.h>
@@ -29,7 +30,7 @@ extern "C" int glx_knn_stats(double stats[16]) {
 static thread_local glx_knn_options g_knn_opt = {0, 0, 0, -1};
 extern "C" int glx_knn_set_options(const glx_knn_options* opt) {
   if (!opt) { g_knn_opt = {0, 0, 0, -1}; return GLX_OK; }
-  GLX_CHECK(opt->filter >= 0 && opt->filter <= 2 && opt->lists >= 0 && opt->lists <= 2 && opt->nsplit >= 0 && opt->nsplit <= 8 &&
+  GLX_CHECK(opt->filter >= 0 && opt->filter <= 2 && opt->lists >= 0 && opt->lists <= 2 && opt->nsplit >= 0 && opt->nsplit <= 32 &&
             opt->concat >= -1 && opt->concat <= 2, GLX_EINVAL, "glx_knn_set_options: value out of range");
   g_knn_opt = *opt;
   return GLX_OK;
@@ -120,7 +121,7 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
   GLX_CHECK(k <= n, GLX_EINVAL, "glx_knn_bruteforce: k=%d exceeds the number of points %lld", k, (long long)n);
   GLX_CHECK(n < (1ll << 31) - BR_MAX, GLX_EINVAL, "glx_knn_bruteforce: n must fit int32");
   GLX_CHECK(0 <= q0 && q0 <= q1 && q1 <= n, GLX_EINVAL, "glx_knn_bruteforce: bad query range");
-  GLX_CHECK(k <= 60, GLX_EUNSUPPORTED, "glx_knn_bruteforce: k=%d (incl. self) above the supported 60", k);
+  GLX_CHECK(k <= KNN_K_MAX, GLX_EUNSUPPORTED, "glx_knn_search: k=%d (incl. self) above the supported %d", k, KNN_K_MAX);
   GLX_CHECK(d <= 16382, GLX_EUNSUPPORTED, "glx_knn_bruteforce: d=%d above the supported 16382", d);
   const int64_t nq = q1 - q0;
   if (nq == 0) return GLX_OK;
@@ -142,6 +143,11 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
   // The same argument one size up: 16 entries for k <= 28 (3e-7 per query at k = 28), 32 for k <= 60.
   const bool short_lists = !long_lists && d + 2 <= 132 && g_knn_opt.lists != 2;
   if (short_lists) KP = k <= 12 ? 8 : (k <= 28 ? 16 : 32);
+  // The wide plan (k > 60): lists of 32 wherever the short lists apply (d + 2 <= 132: the split-bf16 filter for d <= 128, the
+  // fp32-input one for d = 129, 130), of 64 (the fp32-input filter) for the long lists and d > 130; ref ranges such that the
+  // 2 nsplit lists hold about 4 k candidates (below)
+  const bool wide = k > KNN_K_NARROW;
+  if (wide) KP = short_lists ? 32 : 64;
   int DH = knn_kb(KP), nkb = 1;
   if (d + 2 <= 132 && !(KP == 64 && d + 2 > 36)) {   // (KP = 64 lists + a wide double-buffered tile exceed the LDS)
     for (int cand : {8, 12, 18, 34, 66})
@@ -169,13 +175,37 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
     nsplit = (int)std::max<int64_t>(nsplit, std::min<int64_t>(want, ntiles));
   }
   if (g_knn_opt.nsplit > 0) nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, ntiles), g_knn_opt.nsplit));
+  if (wide) {
+    // 2 nsplit lists of KP, nsplit a power of two in [8, 32] (or the number of ref tiles when there are fewer: n = 257 gives 9):
+    // lists * KP >= 4 k where 32 ranges allow it (k <= 128 with 32 entries: 16 lists, 512 candidates; k = 1024 with 64 entries:
+    // 64 lists).  A query's k nearest then fill a list to a quarter on average,
+    // and the smallest full list's threshold lies well beyond the k-th distance.  Above k = 512 the 64 lists of 32 hold 2 k: half
+    // full on average, 1.9 % of config 2's rows go to the fallback at k = 1024 -- and the search takes half the time of the fp32
+    // filter's 64 lists of 64 (34 vs 65 ms of kernels, profiles/knn_wide_k.txt).  With fewer tiles than that (n < 32 nsplit)
+    // every range is one tile of 32 refs, whose half of 16 fits any list: all refs are candidates.  An override never goes below
+    // k candidates.
+    int want = 8;
+    while (want < 32 && 2 * want * KP < 4 * k) want *= 2;
+    if (g_knn_opt.nsplit > 0) want = std::max(g_knn_opt.nsplit, (k + 2 * KP - 1) / (2 * KP));
+    nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, ntiles), want));
+  }
   const int lists = nsplit * 2;
   const int ncand = lists * KP;
   int M = 64;
   while (M < ncand) M *= 2;
+  // wide: the queries in chunks whose candidates (8 bytes each) stay within a fixed budget -- 2.3 GB at 70 000 rows x 4096
+  // candidates otherwise, 33 GB at 10^6; the lists of k <= 60 are short enough to be held for all queries at once
+  const int64_t chunk = wide ? std::min<int64_t>(nq, std::max<int64_t>(BQ, (int64_t)((KNN_CAND_BUDGET / ((size_t)ncand * 8)) / BQ * BQ))) : nq;
+  const int64_t nchunks = (nq + chunk - 1) / chunk;
 
   // (host buffers of the cell order: declared in front of `b`, whose destructor drains the stream they are filled through)
   std::vector<int> oc_sample, oc_cid, oc_perm, oc_place;
+  // the wide plan's timing events of the chunks before the last (destroyed after `b`'s destructor has drained the stream)
+  struct ChunkEvents {
+    std::vector<hipEvent_t> ev;
+    ~ChunkEvents() { for (hipEvent_t e : ev) hipEventDestroy(e); }
+  } chunk_ev;
+  std::vector<std::array<hipEvent_t, 3>> chunk_marks;   // per chunk: start, filter done, re-rank done
   std::vector<double> oc_cen;
   KnnBufs b;
   {
@@ -329,8 +359,8 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
   const double cerr = use_bf16 ? 2.0 * (std::ldexp(1.0, -17) + (1.5 * (3.0 * dpa + 4.0) + d + 16.0) * std::ldexp(1.0, -24))
                                : (double)(dpa + 8) * std::ldexp(1.0, -22);
   GLX_POOL(glx_pool_alloc((void**)&b.qnorm, (size_t)n * 4));
-  GLX_POOL(glx_pool_alloc((void**)&b.cand_d, (size_t)nq * ncand * 4));
-  GLX_POOL(glx_pool_alloc((void**)&b.cand_i, (size_t)nq * ncand * 4));
+  GLX_POOL(glx_pool_alloc((void**)&b.cand_d, (size_t)chunk * ncand * 4));
+  GLX_POOL(glx_pool_alloc((void**)&b.cand_i, (size_t)chunk * ncand * 4));
   GLX_POOL(glx_pool_alloc((void**)&b.flags, (size_t)nq * 4));
   GLX_POOL(glx_pool_alloc((void**)&b.dk2, (size_t)nq * 8));
   GLX_POOL(glx_pool_alloc((void**)&b.nbad, 4));
@@ -343,12 +373,13 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
   stamp("centred, norms bounded");
   GLX_HIP(hipEventRecord(b.e0, st));
   int rc;
+  int cat = 0;
   g_knn_stats[9] = 0.0;      // (the fp32 filter has no concatenated form: not the previous search's value)
   if (use_bf16) {
     // 17 <= d <= 21 (two blocks of 16 per half): the three split products as ONE contraction over concatenated operands,
     // 4 MFMAs per 32 x 32 tile instead of 6 (d <= 16 needs 3 either way)
     // ... and for d <= 20 with the norm folded in (glx_knn_options::concat = 1: without the fold, 0: blocks of 16 features)
-    int cat = (d <= KNN_CAT_SEG && NKB == 2) ? (d < KNN_CAT_SEG ? 2 : 1) : 0;
+    cat = (d <= KNN_CAT_SEG && NKB == 2) ? (d < KNN_CAT_SEG ? 2 : 1) : 0;
     if (g_knn_opt.concat >= 0) cat = std::min(cat, g_knn_opt.concat);
     GLX_POOL(glx_pool_alloc((void**)&b.Xb, (size_t)(n + KNN_PAD_ROWS) * 2 * dpa * 2));
     GLX_POOL(glx_pool_alloc((void**)&b.nrm, (size_t)(n + KNN_PAD_ROWS) * 4));
@@ -369,7 +400,8 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
     const bool cells = cell_starts != nullptr && ncells > 1;
     // sample the block's own cells: every tile of small cells, every 8th of cells of >= 128 tiles
     const int seed_sub = cells ? (int)std::max<int64_t>(1, std::min<int64_t>(8, std::max<int64_t>(1, ntiles / ncells) / 16)) : 0;
-    const bool seeded = cells && 2 * KP >= k;
+    // (not for the wide plan: its lists hold a fraction of k each, and the search stays all pairs -- on the reordered rows if any)
+    const bool seeded = cells && 2 * KP >= k && !wide;
     g_knn_stats[10] = seeded ? (double)seed_sub : 0.0;
     g_knn_stats[11] = 0.0;
     g_knn_stats[12] = 0.0;
@@ -412,20 +444,47 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
       GLX_HIP(hipGetLastError());
       g_knn_stats[12] = (double)ncells;
     }
-    rc = knn_launch_tile_bf16(KP, NKB, b, n, q0, q1, nsplit, st, cat, false);
   } else {
     GLX_POOL(glx_pool_alloc((void**)&b.Rf, (size_t)n * dpa * 4));
     GLX_POOL(glx_pool_alloc((void**)&b.Qf, (size_t)n * dpa * 4));
     hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean,
                        n, d, dpa, b.Rf, b.Qf, b.qnorm);
     GLX_HIP(hipGetLastError());
-    rc = knn_launch_tile_f32(KP, DH, nkb, b, n, q0, q1, nsplit, st);
   }
-  if (rc) return rc;
-  GLX_HIP(hipEventRecord(b.e1, st));
-  rc = knn_launch_rerank(b, n, d, k, q0, nq, lists, KP, M, cerr, st);
-  if (rc) return rc;
-  GLX_HIP(hipEventRecord(b.e2, st));
+  auto launch_tile = [&](int64_t c0, int64_t c1) {
+    return use_bf16 ? knn_launch_tile_bf16(KP, NKB, b, n, c0, c1, nsplit, st, cat, false) : knn_launch_tile_f32(KP, DH, nkb, b, n, c0, c1, nsplit, st);
+  };
+  if (!wide) {
+    rc = launch_tile(q0, q1);
+    if (rc) return rc;
+    GLX_HIP(hipEventRecord(b.e1, st));
+    rc = knn_launch_rerank(b, n, d, k, q0, nq, lists, KP, M, cerr, st);
+    if (rc) return rc;
+    GLX_HIP(hipEventRecord(b.e2, st));
+  } else {
+    // chunk by chunk: filter, re-rank (flags, dk2 and the flagged rows are numbered within the pass, the lists go to their final rows).
+    // Every chunk's stage boundaries have events of their own, read once the stream has drained: the host never waits between chunks.
+    hipEvent_t start = b.e0;
+    for (int64_t c0 = q0; c0 < q1; c0 += chunk) {
+      const int64_t c1 = std::min(q1, c0 + chunk);
+      if (c0 > q0) GLX_HIP(hipMemsetD32Async((hipDeviceptr_t)b.gtau, 0x7f800000, (size_t)(c1 - c0), st));   // (the filter's thresholds are per chunk row)
+      rc = launch_tile(c0, c1);
+      if (rc) return rc;
+      hipEvent_t et = b.e1, er = b.e2;                 // (the last chunk ends on the pass's own events: the fallback is timed from e2)
+      if (c1 < q1) {
+        GLX_HIP(hipEventCreate(&et));
+        chunk_ev.ev.push_back(et);
+        GLX_HIP(hipEventCreate(&er));
+        chunk_ev.ev.push_back(er);
+      }
+      GLX_HIP(hipEventRecord(et, st));
+      rc = knn_launch_rerank_wide(b, n, d, k, q0, c0, c1 - c0, lists, KP, M, cerr, st);
+      if (rc) return rc;
+      GLX_HIP(hipEventRecord(er, st));
+      chunk_marks.push_back({start, et, er});
+      start = er;
+    }
+  }
   float h_rmax[2] = {0.f, 0.f};
   int h_nbad = 0;
   GLX_HIP(hipMemcpyAsync(&h_nbad, b.nbad, 4, hipMemcpyDeviceToHost, st));
@@ -440,7 +499,7 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
   stamp("tile + re-rank done, flags on the host");
   GLX_CHECK(h_rmax[1] == 1.0f, GLX_EINVAL, "glx_knn_bruteforce: non-finite input");   // (the first host look at the centring pass)
   struct { size_t n; size_t size() const { return n; } bool empty() const { return n == 0; } } rows = {(size_t)h_nbad};   // (the list itself is on the device: b.rows)
-  if (short_lists && rows.size() > 64) {
+  if (short_lists && KP < 64 && rows.size() > 64) {
     // repair row by row, or search again with the long lists?  A fallback row streams the data once (measured: ~5 TB/s);
     // the repeat costs about four tile-kernel times (fp32-input filter, longer lists)
     // The first pass is priced by a MODEL, not by its measured time: the choice must not depend on who else uses the GPU (with six
@@ -450,13 +509,33 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
     const double share = b.visited ? std::max(g_knn_stats[11], 0.01) : 1.0;
     // (the fp32-input filter runs at a quarter of that: profiles/r02_knn_filter_probe.txt, d = 64 / 128; 0.03 ms: launches + the host look of a tiny pass)
     const double ms_first = std::max(0.03, (double)nq * (double)n * share * ((double)dpa / 16.0) / 1.26e10 * (use_bf16 ? 1.0 : 4.0));
-    const double ms_rows = (double)rows.size() * ((double)n * d * 8.0 / 5e9);        // (one pass per row: knn_fallback_collect_kernel)
-    if (ms_rows > 4.0 * ms_first) {
+    // (one pass per row: knn_fallback_collect_kernel; wide: plus the ranking of about k refs per row, 12 ns each -- measured at
+    // config 2, k = 1024: 1332 rows in 19.4 ms)
+    const double ms_rows = (double)rows.size() * ((double)n * d * 8.0 / 5e9 + (wide ? 1.2e-5 * k : 0.0));
+    // (the wide plan's repeat -- the fp32-input filter with lists of 64 over as many ranges, and the re-rank of up to 4096
+    // candidates -- measured 52 and 83 times the model's first pass at config 2, k = 512 and 1024: priced at 60)
+    if (ms_rows > (wide ? 60.0 : 4.0) * ms_first) {
       g_knn_stats[2] = (double)rows.size();
       return KNN_ESCALATE;
     }
   }
-  if (!rows.empty()) {
+  if (!rows.empty() && wide) {
+    // the one-pass buffer from k (a power of two >= 2 k), sorted in LDS; rows in batches whose k-round buffers stay within 256 MiB
+    const size_t nr = rows.size();
+    int cap = FB_CAP;
+    while (cap < 2 * k) cap *= 2;
+    const size_t per_row = (size_t)FB_SPLIT * k * 12 + (size_t)cap * 12 + 8;
+    const size_t batch = std::max<size_t>(1, std::min(nr, ((size_t)256 << 20) / per_row));
+    GLX_POOL(glx_pool_alloc((void**)&b.fb_pd, batch * FB_SPLIT * k * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.fb_pi, batch * FB_SPLIT * k * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.fb_cnt, batch * 2 * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.fb_bd, batch * cap * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.fb_bi, batch * cap * 4));
+    for (size_t r0 = 0; r0 < nr; r0 += batch) {
+      rc = knn_launch_fallback_wide(b, n, d, k, q0, b.rows + r0, std::min(batch, nr - r0), cap, st);
+      if (rc) return rc;
+    }
+  } else if (!rows.empty()) {
     const size_t nr = rows.size();
     GLX_POOL(glx_pool_alloc((void**)&b.fb_pd, nr * FB_SPLIT * k * 8));
     GLX_POOL(glx_pool_alloc((void**)&b.fb_pi, nr * FB_SPLIT * k * 4));
@@ -493,6 +572,16 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
   GLX_HIP(hipEventElapsedTime(&ms_tile, b.e0, b.e1));
   GLX_HIP(hipEventElapsedTime(&ms_rr, b.e1, b.e2));
   GLX_HIP(hipEventElapsedTime(&ms_fb, b.e2, b.e3));
+  if (wide) {                // (the sum over the chunks; a later chunk's filter time includes the reset of the thresholds)
+    ms_tile = ms_rr = 0;
+    for (const auto& m : chunk_marks) {
+      float t = 0, r = 0;
+      GLX_HIP(hipEventElapsedTime(&t, m[0], m[1]));
+      GLX_HIP(hipEventElapsedTime(&r, m[1], m[2]));
+      ms_tile += t;
+      ms_rr += r;
+    }
+  }
   g_knn_stats[0] = ms_tile;
   g_knn_stats[1] = ms_rr;
   g_knn_stats[2] = (double)rows.size();
@@ -501,6 +590,9 @@ static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_
   g_knn_stats[5] = (double)dpa;
   g_knn_stats[6] = (double)nsplit;
   g_knn_stats[7] = use_bf16 ? -(double)KP : (double)KP;   // negative: the bf16 filter ran
+  g_knn_stats[13] = (double)nchunks;
+  g_knn_stats[14] = wide ? 1.0 : 0.0;
+  g_knn_stats[15] = (double)ncand;
   return GLX_OK;
 }
 
@@ -522,11 +614,14 @@ extern "C" int glx_knn_bruteforce(const double* X, int64_t n, int d, int k, int 
                                   int device) {
   GLX_CHECK(similarity == 0, GLX_EINVAL,
             "glx_knn_bruteforce: similarity %d; only euclidean (0) -- normalise rows on the host for angular", similarity);
+  GLX_CHECK(k <= KNN_K_NARROW, GLX_EUNSUPPORTED, "glx_knn_bruteforce: k=%d (incl. self) above the supported %d (glx_knn_search takes up to %d)", k,
+            KNN_K_NARROW, KNN_K_MAX);
   return knn_run(X, n, d, k, 0, n, ind_out, dist_out, device);
 }
 
 extern "C" int glx_knn_bruteforce_range(const double* X, int64_t n, int d, int k, int64_t q_begin, int64_t q_end,
                                         int64_t* ind_out, double* dist_out, int device) {
+  GLX_CHECK(k <= KNN_K_NARROW, GLX_EUNSUPPORTED, "glx_knn_bruteforce_range: k=%d (incl. self) above the supported %d", k, KNN_K_NARROW);
   return knn_run(X, n, d, k, q_begin, q_end, ind_out, dist_out, device);
 }
 
@@ -538,6 +633,7 @@ extern "C" int glx_knn_bruteforce_range(const double* X, int64_t n, int d, int k
 extern "C" int glx_knn_cells_range(const double* X, int64_t n, int d, int k, const int64_t* cell_starts, int ncells, int64_t q_begin,
                                    int64_t q_end, int64_t* ind_out, double* dist_out, int device) {
   GLX_CHECK(cell_starts && ncells >= 1, GLX_EINVAL, "glx_knn_cells_range: null argument");
+  GLX_CHECK(k <= KNN_K_NARROW, GLX_EUNSUPPORTED, "glx_knn_cells_range: k=%d (incl. self) above the supported %d", k, KNN_K_NARROW);
   GLX_CHECK(ncells <= 4096, GLX_EUNSUPPORTED, "glx_knn_cells_range: %d cells above the supported 4096", ncells);
   GLX_CHECK(cell_starts[0] == 0, GLX_EINVAL, "glx_knn_cells_range: the first cell must start at row 0");
   for (int c = 1; c < ncells; ++c)
@@ -552,6 +648,7 @@ extern "C" int glx_knn_cells_range(const double* X, int64_t n, int d, int k, con
 // ncells < -1: the rows reordered by -ncells chained cells, then all pairs (coherent wavefronts below the size where pruning pays).
 extern "C" int glx_knn_clustered(const double* X, int64_t n, int d, int k, int ncells, int64_t* ind_out, double* dist_out, int device) {
   GLX_CHECK(ncells >= -4096 && ncells <= 4096, GLX_EINVAL, "glx_knn_clustered: ncells=%d outside [-4096, 4096]", ncells);
+  GLX_CHECK(k <= KNN_K_NARROW, GLX_EUNSUPPORTED, "glx_knn_clustered: k=%d (incl. self) above the supported %d", k, KNN_K_NARROW);
   return knn_run(X, n, d, k, 0, n, ind_out, dist_out, device, nullptr, nullptr, 0, ncells);
 }
 
@@ -566,6 +663,7 @@ extern "C" int glx_knn_search(const double* X, int64_t n, int d, int k, int ncel
   GLX_CHECK(out, GLX_EINVAL, "glx_knn_search: null output");
   *out = nullptr;
   GLX_CHECK(ncells >= -4096 && ncells <= 4096, GLX_EINVAL, "glx_knn_search: ncells=%d outside [-4096, 4096]", ncells);
+  GLX_CHECK(k <= KNN_K_MAX, GLX_EUNSUPPORTED, "glx_knn_search: k=%d (incl. self) above the supported %d", k, KNN_K_MAX);
   glx_knn_result* res = new glx_knn_result();
   const auto t_call = std::chrono::steady_clock::now();
   const int rc = knn_run(X, n, d, k, 0, n, nullptr, nullptr, device, res, nullptr, 0, (ncells > 1 || ncells < -1) ? ncells : 0);

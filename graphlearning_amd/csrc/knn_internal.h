@@ -27,6 +27,9 @@ static const int CELL_SPLIT = 64;      // workgroups per cell in the centre / ra
 static const int FB_SPLIT = 64;        // pieces a fallback row's refs are cut into
 static const int FB_CACHE = 2048;      // a piece of at most this many refs keeps its distances in LDS between the rounds
 static const int FB_CAP = 128;         // candidates per row the one-pass fallback can hold
+static const int KNN_K_NARROW = 60;    // neighbours (self included) of the list-returning entry points and of the register re-rank
+static const int KNN_K_MAX = 1024;     // neighbours (self included) of the wide search (glx_knn_search)
+static const size_t KNN_CAND_BUDGET = (size_t)1 << 30;   // bytes of candidates (value + index) a wide pass holds at once: its query chunks
 
 // features per half per block of the blocked (d > 130) fp32 variant; 16 where the KP = 64 lists leave less LDS
 constexpr int knn_kb(int KP) { return KP == 64 ? 16 : 32; }   // (KP = 8 never takes the blocked variant)
@@ -144,3 +147,9 @@ __global__ __launch_bounds__(256) void knn_runs_kernel(const unsigned char* __re
 int knn_launch_rerank(const KnnBufs& b, int64_t n, int d, int k, int64_t q0, int64_t nq, int lists, int KP, int M, double cerr, hipStream_t st);
 // the flagged rows (nr of them, listed in b.rows) redone exactly; fb_runs: the tile runs of a cell-pruned search (or null), BR its tile
 int knn_launch_fallback(const KnnBufs& b, int64_t n, int d, int k, int64_t q0, size_t nr, const int* fb_runs, int BR, hipStream_t st);
+// the wide search (60 < k <= KNN_K_MAX): the re-rank of the queries [c0, c0 + nqc) of a pass that started at q_pass (candidates of
+// the chunk in b.cand_d / b.cand_i; flags, dk2 and the flagged rows numbered within the pass), LDS-sorted; and the fallback of the
+// nr flagged rows listed at `rows`, its one-pass buffer holding cap (a power of two >= 2 k) refs per row
+int knn_launch_rerank_wide(const KnnBufs& b, int64_t n, int d, int k, int64_t q_pass, int64_t c0, int64_t nqc, int lists, int KP, int M, double cerr,
+                           hipStream_t st);
+int knn_launch_fallback_wide(const KnnBufs& b, int64_t n, int d, int k, int64_t q0, const int* rows, size_t nr, int cap, hipStream_t st);

@@ -326,12 +326,13 @@ __global__ __launch_bounds__(256) void knn_fallback_collect_kernel(const double*
                                                                    const int* __restrict__ rows, const double* __restrict__ dk2,
                                                                    int* __restrict__ cnt, double* __restrict__ buf_d, int* __restrict__ buf_i,
                                                                    const int* __restrict__ orig, const int* __restrict__ runs,
-                                                                   const int* __restrict__ nruns, int maxruns, int BR) {
+                                                                   const int* __restrict__ nruns, int maxruns, int BR, int cap) {
+  // cap: the buffer's slots per row (FB_CAP; the wide search sizes it from k)
   const int row = blockIdx.x, piece = blockIdx.y;
   const int64_t ql = rows[row];
   const double bound = dk2[ql];
   if (!(bound < INFINITY)) {
-    if (piece == 0 && threadIdx.x == 0) cnt[row] = FB_CAP + 1;
+    if (piece == 0 && threadIdx.x == 0) cnt[row] = cap + 1;
     return;
   }
   const double* xq = X + (q_begin + ql) * d;
@@ -339,9 +340,9 @@ __global__ __launch_bounds__(256) void knn_fallback_collect_kernel(const double*
     const double dd = sqdist_exact(xq, X + ref * d, d);
     if (dd <= bound) {
       const int slot = atomicAdd(&cnt[row], 1);
-      if (slot < FB_CAP) {
-        buf_d[(size_t)row * FB_CAP + slot] = dd;
-        buf_i[(size_t)row * FB_CAP + slot] = orig ? orig[ref] : (int)ref;
+      if (slot < cap) {
+        buf_d[(size_t)row * cap + slot] = dd;
+        buf_i[(size_t)row * cap + slot] = orig ? orig[ref] : (int)ref;
       }
     }
   };
@@ -466,7 +467,7 @@ int knn_launch_fallback(const KnnBufs& b, int64_t n, int d, int k, int64_t q0, s
   int* redo = b.fb_cnt + nr;
   // one pass: every ref within the bound the re-rank left, ranked by a wavefront per row
   hipLaunchKernelGGL(knn_fallback_collect_kernel, dim3((unsigned)nr, FB_SPLIT), dim3(256), 0, st, (const double*)b.X, n, d, q0, (const int*)b.rows,
-                     (const double*)b.dk2, b.fb_cnt, b.fb_bd, b.fb_bi, (const int*)b.orig, fb_runs, (const int*)b.nruns, b.maxruns, BR);
+                     (const double*)b.dk2, b.fb_cnt, b.fb_bd, b.fb_bi, (const int*)b.orig, fb_runs, (const int*)b.nruns, b.maxruns, BR, FB_CAP);
   hipLaunchKernelGGL(knn_fallback_select_kernel, dim3((unsigned)nr), dim3(64), 0, st, (const int*)b.fb_cnt, (const double*)b.fb_bd, (const int*)b.fb_bi,
                      (const int*)b.rows, (int)nr, k, b.ind, b.dist, (const int*)b.orig, q0, redo);
   // the k-round kernels: only the rows the one pass could not finish (their workgroups return at once otherwise)
@@ -474,6 +475,183 @@ int knn_launch_fallback(const KnnBufs& b, int64_t n, int d, int k, int64_t q0, s
                      b.fb_pd, b.fb_pi, (const int*)b.orig, fb_runs, (const int*)b.nruns, b.maxruns, BR, (const int*)redo);
   hipLaunchKernelGGL(knn_fallback_merge_kernel, dim3((unsigned)nr), dim3(64), 0, st, (const double*)b.fb_pd, (const int*)b.fb_pi,
                      (const int*)b.rows, (int)nr, k, b.ind, b.dist, (const int*)b.orig, q0, (const int*)redo);
+  GLX_HIP(hipGetLastError());
+  return GLX_OK;
+}
+
+// ---- the wide search (k > 60): re-rank and fallback for lists of up to 1024 ------------------------------------------------------
+// The kernels above hold a query's candidates in one wavefront's registers and write slot e from lane e of register 0 (k < 64);
+// their fp32 screen ranks every candidate against every other (O(M^2)).  Here a workgroup of 256 sorts in LDS: the filter values
+// (the k-th smallest of them bounds what can matter), then the (distance, index) pairs of the few that remain.
+
+// ascending bitonic sort of P (a power of two) keys in LDS by the whole workgroup (the caller has synchronised the writes)
+__device__ __forceinline__ void lds_sort_keys(float* sk, int P) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
+        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const float a = sk[lo], c = sk[hi];
+        if (up ? c < a : a < c) { sk[lo] = c; sk[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// ascending bitonic sort of P (a power of two) (distance, index) pairs in LDS by the whole workgroup
+__device__ __forceinline__ void lds_sort_pairs(double* sd, int* si, int P) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
+        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const double dl = sd[lo], dh = sd[hi];
+        const int il = si[lo], ih = si[hi];
+        if (up ? lex_less(dh, ih, dl, il) : lex_less(dl, il, dh, ih)) { sd[lo] = dh; sd[hi] = dl; si[lo] = ih; si[hi] = il; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// One workgroup per query of the chunk [q_begin, q_begin + nq) of a pass that started at q_pass.  The same rule as knn_rerank_kernel:
+// with v_k the k-th smallest filter value, only candidates within v_k + 4 eps can be among the k nearest; those get exact fp64
+// distances (sqdist_exact), are sorted by (distance, caller index), and the first k go out.  The acceptance test is unchanged: every
+// full list's threshold must be at least dk2 + 2 eps.  flags / dk2_out / badrows are indexed by the row within the PASS (the
+// fallback's numbering); cand_d / cand_i by the row within the chunk.  LDS: M * 16 bytes (64 KB at M = 4096).
+__global__ __launch_bounds__(256) void knn_rerank_wide_kernel(const double* __restrict__ X, int64_t n, int d, int k, int64_t q_begin, int64_t nq,
+                                                              int64_t q_pass, const float* __restrict__ cand_d, const int* __restrict__ cand_i,
+                                                              int lists, int KP, int M, const float* __restrict__ qnorm,
+                                                              const float* __restrict__ rmax_p, double cerr, int64_t* __restrict__ ind_out,
+                                                              double* __restrict__ dist_out, int* __restrict__ flags, const int* __restrict__ orig,
+                                                              double* __restrict__ dk2_out, int* __restrict__ nbad, int* __restrict__ badrows) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];
+  double* sd = (double*)sm;          // [M] exact distances of the survivors
+  int* si = (int*)(sd + M);          // [M] their caller indices
+  float* sv = (float*)(si + M);      // [M] filter values by candidate slot (+inf: empty slot)
+  float* sk = (float*)sd;            // [M] the same values sorted (sd's space, before the first exact distance is written)
+  __shared__ int s_cnt;
+  const int64_t ql = blockIdx.x;
+  if (ql >= nq) return;
+  const int tid = threadIdx.x;
+  const int64_t q = q_begin + ql, qp = q - q_pass;
+  const int ncand = lists * KP;
+  const float* cd = cand_d + ql * ncand;
+  const int* cx = cand_i + ql * ncand;
+  for (int c = tid; c < M; c += 256) {
+    float v = INFINITY;
+    if (c < ncand) {
+      const int ci = cx[c];
+      if (ci >= 0 && ci < n) v = cd[c];
+    }
+    sv[c] = v;
+    sk[c] = v;
+  }
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+  lds_sort_keys(sk, M);
+  const float vk = sk[k - 1];
+  const double rq0 = (double)qnorm[q] + (double)rmax_p[0];
+  const double eps0 = cerr * rq0 * rq0;
+  const double keep = (double)vk + 4.0 * eps0 + 1e-6 * fabs((double)vk);     // (+inf when fewer than k slots are filled)
+  __syncthreads();                   // (every thread has read sk: sd's space is free)
+  const double* xq = X + q * d;
+  for (int c = tid; c < ncand; c += 256) {
+    const int ci = cx[c];
+    if (ci >= 0 && ci < n && (double)sv[c] <= keep) {
+      const int slot = atomicAdd(&s_cnt, 1);         // (slot order is arbitrary: the sort below orders by (distance, unique index))
+      sd[slot] = sqdist_exact(xq, X + (int64_t)ci * d, d);
+      si[slot] = orig ? orig[ci] : ci;
+    }
+  }
+  __syncthreads();
+  const int S = s_cnt;
+  int P = 1;
+  while (P < S || P < k) P <<= 1;                    // (<= M: S <= ncand and k <= ncand, knn_launch_rerank_wide)
+  for (int c = S + tid; c < P; c += 256) { sd[c] = INFINITY; si[c] = 0x7fffffff; }
+  __syncthreads();
+  lds_sort_pairs(sd, si, P);
+  const int64_t orow = orig ? (int64_t)orig[q] - q_pass : qp;
+  for (int c = tid; c < k; c += 256) {
+    ind_out[orow * k + c] = si[c] == 0x7fffffff ? -1 : si[c];
+    dist_out[orow * k + c] = sqrt(sd[c]);
+  }
+  const double dk2 = sd[k - 1];
+  int bad = 0;
+  for (int l = tid; l < lists; l += 256) {
+    float tau = 0.f;
+    for (int p = 0; p < KP; ++p) tau = fmaxf(tau, cd[l * KP + p]);
+    if (tau < INFINITY && !((double)tau >= dk2 + 2.0 * eps0)) bad = 1;
+  }
+  bad = __syncthreads_or(bad) || !(dk2 < INFINITY);
+  if (tid == 0) {
+    flags[qp] = bad;
+    if (bad) {
+      dk2_out[qp] = dk2;
+      badrows[atomicAdd(nbad, 1)] = (int)qp;
+    }
+  }
+}
+
+int knn_launch_rerank_wide(const KnnBufs& b, int64_t n, int d, int k, int64_t q_pass, int64_t c0, int64_t nqc, int lists, int KP, int M, double cerr,
+                           hipStream_t st) {
+  GLX_CHECK(k <= lists * KP && M >= lists * KP && M <= 4096 && (M & (M - 1)) == 0, GLX_EINVAL,
+            "knn: the wide re-rank needs k <= candidates <= M <= 4096 (k=%d, %d x %d candidates, M=%d)", k, lists, KP, M);
+  const size_t shm = (size_t)M * 16;
+  GLX_HIP(hipFuncSetAttribute((const void*)knn_rerank_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  hipLaunchKernelGGL(knn_rerank_wide_kernel, dim3((unsigned)nqc), dim3(256), shm, st, (const double*)b.X, n, d, k, c0, nqc, q_pass,
+                     (const float*)b.cand_d, (const int*)b.cand_i, lists, KP, M, (const float*)b.qnorm, (const float*)b.rmax, cerr, b.ind, b.dist,
+                     b.flags, (const int*)b.orig, b.dk2, b.nbad, b.rows);
+  GLX_HIP(hipGetLastError());
+  return GLX_OK;
+}
+
+// The one-pass fallback's ranking for wide k: the row's collected refs (at most cap, a power of two >= 2 k) sorted in LDS.  Rows whose
+// buffer overflowed are marked for the k-round kernels as in knn_fallback_select_kernel.
+__global__ __launch_bounds__(256) void knn_fallback_select_wide_kernel(const int* __restrict__ cnt, const double* __restrict__ buf_d,
+                                                                       const int* __restrict__ buf_i, const int* __restrict__ rows, int nrows, int k,
+                                                                       int cap, int64_t* __restrict__ ind_out, double* __restrict__ dist_out,
+                                                                       const int* __restrict__ orig, int64_t q_begin, int* __restrict__ redo) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];
+  double* sd = (double*)sm;          // [cap]
+  int* si = (int*)(sd + cap);        // [cap]
+  const int row = blockIdx.x, tid = threadIdx.x;
+  if (row >= nrows) return;
+  const int c = cnt[row];
+  if (c > cap || c < k) {
+    if (tid == 0) redo[row] = 1;
+    return;
+  }
+  if (tid == 0) redo[row] = 0;
+  const int64_t ql = orig ? (int64_t)orig[q_begin + rows[row]] - q_begin : rows[row];
+  int P = 1;
+  while (P < c) P <<= 1;             // (<= cap)
+  for (int e = tid; e < P; e += 256) {
+    sd[e] = e < c ? buf_d[(size_t)row * cap + e] : INFINITY;
+    si[e] = e < c ? buf_i[(size_t)row * cap + e] : 0x7fffffff;
+  }
+  __syncthreads();
+  lds_sort_pairs(sd, si, P);
+  for (int e = tid; e < k; e += 256) {
+    ind_out[ql * k + e] = si[e];
+    dist_out[ql * k + e] = sqrt(sd[e]);
+  }
+}
+
+// nr flagged rows (rows: their numbers within the pass) redone exactly; all pairs (the wide search never prunes cells).  Buffers:
+// b.fb_cnt [2 nr], b.fb_bd / b.fb_bi [nr * cap], b.fb_pd / b.fb_pi [nr * FB_SPLIT * k].
+int knn_launch_fallback_wide(const KnnBufs& b, int64_t n, int d, int k, int64_t q0, const int* rows, size_t nr, int cap, hipStream_t st) {
+  int* redo = b.fb_cnt + nr;
+  GLX_HIP(hipMemsetAsync(b.fb_cnt, 0, nr * 2 * 4, st));
+  hipLaunchKernelGGL(knn_fallback_collect_kernel, dim3((unsigned)nr, FB_SPLIT), dim3(256), 0, st, (const double*)b.X, n, d, q0, rows,
+                     (const double*)b.dk2, b.fb_cnt, b.fb_bd, b.fb_bi, (const int*)b.orig, (const int*)nullptr, (const int*)nullptr, 0, 0, cap);
+  hipLaunchKernelGGL(knn_fallback_select_wide_kernel, dim3((unsigned)nr), dim3(256), (size_t)cap * 12, st, (const int*)b.fb_cnt, (const double*)b.fb_bd,
+                     (const int*)b.fb_bi, rows, (int)nr, k, cap, b.ind, b.dist, (const int*)b.orig, q0, redo);
+  hipLaunchKernelGGL(knn_fallback_piece_kernel, dim3((unsigned)nr, FB_SPLIT), dim3(256), 0, st, (const double*)b.X, n, d, k, q0, rows,
+                     b.fb_pd, b.fb_pi, (const int*)b.orig, (const int*)nullptr, (const int*)nullptr, 0, 0, (const int*)redo);
+  hipLaunchKernelGGL(knn_fallback_merge_kernel, dim3((unsigned)nr), dim3(64), 0, st, (const double*)b.fb_pd, (const int*)b.fb_pi,
+                     rows, (int)nr, k, b.ind, b.dist, (const int*)b.orig, q0, (const int*)redo);
   GLX_HIP(hipGetLastError());
   return GLX_OK;
 }

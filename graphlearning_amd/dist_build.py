@@ -5,7 +5,9 @@ N x 70 000 vertices and hopeless at config 4 (n = 10^7: 183 M stored entries per
 only ever touches its own block of rows [lo, hi) of the ORIGINAL vertex numbering:
 
   1. kNN lists of its own query rows (glx_knn_bruteforce_range; every rank holds the features -- the one O(n d)
-     array the brute-force search needs everywhere, SURVEY 8e);
+     array the brute-force search needs everywhere).  That list-returning search keeps its limit of 60
+     neighbours including self, so the sharded build takes k <= 59; the wide search of weightmatrix.knn (up to 1023)
+     exists on one device only;
   2. symmetrisation by owner rank: each list entry (i -> j, w) is also needed by the owner of row j, so the
      entries are routed to their owners with one all-to-all-v of (j, i, w) triples, and every rank assembles ITS
      rows of W = (A + A^T)/2 from its own lists and the triples it received -- with the reference's own scipy

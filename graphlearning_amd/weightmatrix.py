@@ -26,7 +26,8 @@ def knn(data, k, kernel='gaussian', eta=None, symmetrize=True, metric='raw', sim
     rounded exp of csrc/exp_cr.h -- a machine-independent W that agrees with any host's numpy to that host's libm error (about 5 %
     of the weights differ by one ulp from the build container's numpy; tests/test_gpu_weights.py counts them and what they do
     downstream: nothing to the labels or the iteration counts of configs 2 and 3).  GLX_HOST_EXP=1 evaluates numpy's exp on the
-    host instead: the W of THIS host's reference, bit for bit (what the golden-vector suite compares against)."""
+    host instead: the W of THIS host's reference, bit for bit (what the golden-vector suite compares against).
+    k from 1 to min(n, 1024) - 1 (self is counted on top, as in the reference); above 59 the search takes its wide plan."""
     # validate before anything is launched (a bad kernel name must not leave work behind on the device)
     if similarity not in ['angular', 'euclidean']:
         sys.exit('Invalid choice of similarity ' + similarity)
@@ -136,7 +137,9 @@ def knnsearch(X, k, method=None, similarity='euclidean', dataset=None, metric='r
     """k nearest neighbours including the self point (reference weightmatrix.py:297-429).
     Every `method` the reference knows ('kdtree', 'brute', 'annoy', None) is served by the
     exact GPU search ('hip'); 'annoy' is approximate in the reference, exact here.
-    Returns (knn_ind int64 (n,k), knn_dist float64 (n,k)), rows ascending by distance."""
+    Returns (knn_ind int64 (n,k), knn_dist float64 (n,k)), rows ascending by distance.
+    k (self included) from 1 to min(n, 1024): up to 60 the list-returning search (_hip.knn_bruteforce), above it the
+    wide search of a result object (_hip.KnnResult), whose lists are copied out -- the same exact lists either way."""
     if method is None:
         method = 'hip'
     if method not in ['hip', 'kdtree', 'brute', 'annoy']:
@@ -144,7 +147,14 @@ def knnsearch(X, k, method=None, similarity='euclidean', dataset=None, metric='r
     if similarity not in ['angular', 'euclidean']:
         sys.exit('Invalid choice of similarity ' + similarity)
     X = np.asarray(X, dtype=np.float64)
-    knn_ind, knn_dist = _hip.knn_bruteforce(X, int(k), similarity=similarity, device=device)
+    if int(k) <= _hip.KNN_K_LISTS:
+        knn_ind, knn_dist = _hip.knn_bruteforce(X, int(k), similarity=similarity, device=device)
+    else:
+        res = _hip.KnnResult(X, int(k), similarity=similarity, device=device)
+        try:
+            knn_ind, knn_dist = res.lists()
+        finally:
+            res.close()
     if dataset is not None:                  # npz cache 'J','D' (reference :416-427)
         path = os.path.join(knn_dir, dataset.lower() + '_' + metric.lower() + '.npz')
         if not os.path.exists(knn_dir):

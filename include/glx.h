@@ -338,7 +338,8 @@ int glx_knn_cells_range(const double* X, int64_t n, int d, int k, const int64_t*
                         int64_t q_end, int64_t* ind_out, double* dist_out, int device);
 
 /* ---- search results as objects (what weightmatrix.knn uses) ---------------------------------------------------------------------
- * glx_knn_search runs the full search (every row a query, self included; ncells as in glx_knn_clustered: 0 / 1 all pairs,
+ * glx_knn_search runs the full search (every row a query, self included, 1 <= k <= min(n, 1024) -- above 60 the wide plan, above
+ * 1024 GLX_EUNSUPPORTED; ncells as in glx_knn_clustered: 0 / 1 all pairs,
  * > 1 pruned by library-formed cells, < -1 all pairs on rows reordered by -ncells chained cells) and leaves the lists ON THE DEVICE
  * in a result object.  OWNERSHIP: the caller owns *out and releases it with glx_knn_result_destroy; the other calls borrow it.
  * The object may be used from any thread, by one thread at a time; nothing is handed from one call to the next through hidden

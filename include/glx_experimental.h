@@ -103,7 +103,7 @@ int glx_dist_sweep_interior(glx_dist_sweep* s, int want_err, double* err_local_o
 int glx_knn_clustered(const double* X, int64_t n, int d, int k, int ncells, int64_t* ind_out, double* dist_out, int device);
 /* Plan overrides of the calling thread's searches (tests and A/B measurements; NULL or all-default values = the library decides):
  * filter 0 auto | 1 split-bf16 | 2 fp32 operands; lists 0 auto | 1 short | 2 long (one list holds all k neighbours of a query);
- * nsplit 0 auto | 1..8 ref ranges per query block; concat -1 auto | 0 blocks of 16 features | 1 concatenated split operands
+ * nsplit 0 auto | 1..8 ref ranges per query block (1..32 for the wide search, k > 60, never fewer than k candidates); concat -1 auto | 0 blocks of 16 features | 1 concatenated split operands
  * (d <= 21) | 2 with the norm folded in (d <= 20).  Every plan returns the same exact lists. */
 typedef struct { int filter, lists, nsplit, concat; } glx_knn_options;
 int glx_knn_set_options(const glx_knn_options* opt);
@@ -136,7 +136,9 @@ int glx_knn_stats(double stats[16]);  /* of the calling thread's last search: [0
                                         [9] concatenated operands (d <= 21): 0 no, 1 yes, 2 with the norm folded in (d <= 20),
                                         [10] tile stride of the sample the seeding pre-pass looked at (0: no pre-pass; tile-kernel ms
                                         include it and the cell passes), [11] share of the (query block, ref tile) pairs visited and
-                                        [12] number of cells of a cell-pruned search (0: all pairs); [13..15] reserved */
+                                        [12] number of cells of a cell-pruned search (0: all pairs); [13] query chunks of the
+                                        pass (1 unless the wide plan's candidates exceed 1 GiB), [14] 1 if the wide plan ran
+                                        (k > 60), [15] candidates per query (lists x list length) */
 
 /* the smallest relative distance from `tol` of the residual norms that decided the stops of the last tolerance-mode (GLX_CG_TREE)
  * solve on this operator; +inf when there was none.  ssl.laplace / ssl.randomwalk (reduce='auto') hand a solve whose stop hung on less
