@@ -9,7 +9,8 @@
 //      sqeuclidean_distance_double) of the candidates, sorted by (distance, index); a row is accepted only if every candidate
 //      list's threshold exceeds the exact k-th distance by twice a bound on the filter's error;
 //   3. fallback -- rows that fail the check are redone by an exact fp64 scan.
-// This file: one pass of the search (knn_pass), the escalation to long lists, the C-ABI entry points.
+// This file: one pass of the search (knn_pass: the stages of KnnPass in order, planned by knn_plan.h), the escalation to long lists,
+// the C-ABI entry points.
 #include "knn_internal.h"
 #include <array>
 #include <atomic>
@@ -19,10 +20,10 @@
 #include <vector>
 
 // statistics of the calling thread's last search (glx_knn_stats)
-static thread_local double g_knn_stats[16];
+static thread_local double g_knn_stats[KS_COUNT];
 extern "C" int glx_knn_stats(double stats[16]) {
   GLX_CHECK(stats, GLX_EINVAL, "glx_knn_stats: null output");
-  for (int i = 0; i < 16; ++i) stats[i] = g_knn_stats[i];
+  for (int i = 0; i < KS_COUNT; ++i) stats[i] = g_knn_stats[i];
   return GLX_OK;
 }
 
@@ -105,6 +106,393 @@ static int knn_verify_upload(const double* X_host, const double* X_dev, int64_t 
 
 static const int KNN_ESCALATE = 1;    // knn_pass: too many rows failed the acceptance test of the short lists -- search again with long ones
 
+// GLX_TIMING: the host's stage stamps on stderr
+struct KnnStamp {
+  bool on;
+  std::chrono::steady_clock::time_point t0;
+  void operator()(const char* what) const {
+    if (on) fprintf(stderr, "[glx] knn: %-28s %.2f ms since the call\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+
+static int knn_check_args(const double* X, int64_t n, int d, int k, int64_t q0, int64_t q1, const int64_t* ind_out, const double* dist_out,
+                          const glx_knn_result* capture) {
+  GLX_CHECK(X && ((ind_out && dist_out) || capture), GLX_EINVAL, "glx_knn_bruteforce: null argument");
+  GLX_CHECK(!capture || (q0 == 0 && q1 == n), GLX_EINVAL, "glx_knn_search: a result object holds a full search");
+  GLX_CHECK(n >= 1 && d >= 1 && k >= 1, GLX_EINVAL, "glx_knn_bruteforce: need n, d, k >= 1 (n=%lld d=%d k=%d)", (long long)n, d, k);
+  GLX_CHECK(k <= n, GLX_EINVAL, "glx_knn_bruteforce: k=%d exceeds the number of points %lld", k, (long long)n);
+  GLX_CHECK(n < (1ll << 31) - BR_MAX, GLX_EINVAL, "glx_knn_bruteforce: n must fit int32");
+  GLX_CHECK(0 <= q0 && q0 <= q1 && q1 <= n, GLX_EINVAL, "glx_knn_bruteforce: bad query range");
+  GLX_CHECK(k <= KNN_K_MAX, GLX_EUNSUPPORTED, "glx_knn_search: k=%d (incl. self) above the supported %d", k, KNN_K_MAX);
+  GLX_CHECK(d <= 16382, GLX_EUNSUPPORTED, "glx_knn_bruteforce: d=%d above the supported 16382", d);
+  return GLX_OK;
+}
+
+// One pass of the search: the request, its plan, what it works on, and what a stage leaves for the next.  The stages run in the
+// order of their declarations (knn_pass); each returns the library's status.
+struct KnnPass {
+  const double* X;
+  int64_t n;
+  int d, k;
+  int64_t q0, q1, nq;
+  int64_t* ind_out;
+  double* dist_out;
+  int device;
+  bool long_lists;
+  glx_knn_result* capture;
+  const int64_t* cell_starts;   // the cells the rows come in: the caller's, or the ones form_cells made (b.own_starts)
+  int ncells;
+  KnnPlan p;
+  KnnStamp stamp;
+  KnnBufs b;
+  hipStream_t st = nullptr;
+  bool on_host = true;          // X is a host array (else a device pointer)
+  bool perm_pending = false;    // b.orig goes to the result object
+  // the host look at the device's counts (members: the copies into them are asynchronous)
+  float h_rmax[2] = {0.f, 0.f};
+  int h_nbad = 0;
+  unsigned long long h_visited = 0;
+  size_t nbad = 0;              // rows that failed the acceptance test (the list itself is on the device: b.rows)
+
+  int launch_tile(int64_t c0, int64_t c1) {
+    return p.use_bf16 ? knn_launch_tile_bf16(p.KP, p.NKB, b, n, c0, c1, p.nsplit, st, p.cat, false)
+                      : knn_launch_tile_f32(p.KP, p.DH, p.nkb, b, n, c0, c1, p.nsplit, st);
+  }
+
+  // the work set (stream, events) and the features on the device
+  int upload_features() {
+    GLX_UP(glx_work_acquire(device, &b.work));
+    b.stream = b.work->stream;
+    b.e0 = b.work->ev[0]; b.e1 = b.work->ev[1]; b.e2 = b.work->ev[2]; b.e3 = b.work->ev[3];
+    st = b.stream;
+    GLX_POOL(glx_pool_alloc((void**)&b.X, (size_t)n * d * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.mean, d * 8));
+    stamp("stream, events, buffers");
+    // (hipMemcpyDefault: X may also be a DEVICE pointer -- glx_knn_bruteforce_range / glx_knn_cells_range of the sharded build, whose
+    // features are generated, ordered and kept on the GPU; the library-formed cells read sample rows on the host and need a host X)
+    {
+      hipPointerAttribute_t at;
+      on_host = hipPointerGetAttributes(&at, X) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged);
+      (void)hipGetLastError();
+    }
+    if (on_host) {
+      // the caller's (pageable) array goes up through the library's page-locked staging area, checked (glx_internal.h: why)
+      GLX_UP(glx_upload(b.X, X, (size_t)n * d * 8, st, "features of a search"));
+    } else {
+      GLX_HIP(hipMemcpyAsync(b.X, X, (size_t)n * d * 8, hipMemcpyDefault, st));
+    }
+    stamp("X enqueued");
+    if ((g_debug_flags & 1) && on_host) GLX_UP(knn_verify_upload(X, b.X, n, d, st, "after the upload"));
+    return GLX_OK;
+  }
+
+  // Cells formed by the library (auto_cells).  > 1: that many cells (nearest of evenly spaced sample rows), the rows reordered by
+  // cell and searched with the cell pruning of glx_knn_cells_range; the re-rank ranks by and returns the caller's indices.
+  // < -1 (below the size where pruning pays): the rows ARE reordered by -auto_cells chained cells on the device and then searched
+  // all pairs.  The 32 queries of a wavefront then come from one corner of feature space, a ref tile holds candidates for many of
+  // them or for none, and fewer wave-tiles leave the tile kernel's fast path: config 2 2.06 -> 1.83 ms of search wall time, config
+  // 3's shape 3.06 -> 2.63 ms, data without clusters unchanged (profiles/r03_knn_cells_midsize.txt).
+  // Either way the cells are put in a chain of nearest centres (knn_chain_places), then the rows by cell (counting sort, ascending
+  // caller index inside a cell).
+  int form_cells(int auto_cells) {
+    const bool reorder_only = auto_cells < -1;
+    if (auto_cells < -1) auto_cells = -auto_cells;
+    if (!(auto_cells > 1 && q0 == 0 && q1 == n && !long_lists && d <= 128 && n >= 4 * (int64_t)auto_cells)) return GLX_OK;
+    const int m = auto_cells;
+    b.oc_sample.resize(m);
+    for (int c = 0; c < m; ++c) b.oc_sample[c] = (int)(((2 * (int64_t)c + 1) * n) / (2 * (int64_t)m));     // evenly spaced rows
+    GLX_POOL(glx_pool_alloc((void**)&b.cen, (size_t)m * d * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.cell_id, (size_t)std::max<int64_t>(n, m) * 4));
+    GLX_UP(glx_upload(b.cell_id, b.oc_sample.data(), (size_t)m * 4, st, "knn_pass"));
+    hipLaunchKernelGGL(knn_gather_rows_kernel, dim3((unsigned)(((int64_t)m * d + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const int*)b.cell_id,
+                       (int64_t)m, d, b.cen);
+    hipLaunchKernelGGL(knn_assign_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), (size_t)16 * d * 8, st, (const double*)b.X, d, n, (const double*)b.cen, m,
+                       b.cell_id, (d + 31) / 32);
+    GLX_HIP(hipGetLastError());
+    GLX_POOL(glx_pool_alloc((void**)&b.orig, (size_t)n * 4));
+    GLX_UP(reorder_only ? order_cells_on_device(m) : order_cells_on_host(m));
+    b.Xraw = b.X;
+    b.X = nullptr;
+    GLX_POOL(glx_pool_alloc((void**)&b.X, (size_t)n * d * 8));
+    hipLaunchKernelGGL(knn_gather_rows_kernel, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, st, (const double*)b.Xraw, (const int*)b.orig, n, d, b.X);
+    GLX_HIP(hipGetLastError());
+    stamp("rows reordered by cell");
+    return GLX_OK;
+  }
+
+  // reorder only: the chain of the cells from the caller's copy of the sample rows (the same doubles the device gathered), the rows
+  // into cell order by the three knn_cellrank kernels: nothing here waits for the device
+  int order_cells_on_device(int m) {
+    b.oc_cen.resize((size_t)m * d);
+    for (int c = 0; c < m; ++c) memcpy(&b.oc_cen[(size_t)c * d], X + (size_t)b.oc_sample[c] * d, (size_t)d * 8);
+    b.oc_place = knn_chain_places(b.oc_cen, m, d);
+    const int nb = (int)((n + 255) / 256);
+    GLX_POOL(glx_pool_alloc((void**)&b.place, (size_t)m * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.bh, (size_t)(nb + 1) * m * 4));     // (+ one row: the keys' totals / starting positions)
+    GLX_UP(glx_upload(b.place, b.oc_place.data(), (size_t)m * 4, st, "knn_pass"));
+    hipLaunchKernelGGL(knn_cellrank_hist_kernel, dim3((unsigned)nb), dim3(256), (size_t)m * 4, st, b.cell_id, (const int*)b.place, n, m, b.bh);
+    hipLaunchKernelGGL(knn_cellrank_scan_kernel, dim3((unsigned)m), dim3(256), 0, st, b.bh, nb, m);
+    hipLaunchKernelGGL(knn_cellrank_base_kernel, dim3(1), dim3(256), 0, st, b.bh, nb, m);
+    hipLaunchKernelGGL(knn_cellrank_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const int*)b.cell_id, n, m, (const int*)b.bh, nb, b.orig);
+    perm_pending = capture != nullptr;               // the permutation comes back with the results (glx_knn_result_order)
+    return GLX_OK;
+  }
+
+  // the pruned search needs the cells' extents on the host: cell ids and centres come back, the rows are counted into chained
+  // cells here (stable: ascending caller index inside a cell)
+  int order_cells_on_host(int m) {
+    b.oc_cid.resize(n);
+    b.oc_cen.resize((size_t)m * d);
+    GLX_UP(glx_download(b.oc_cid.data(), b.cell_id, (size_t)n * 4, st, "knn_pass"));
+    GLX_UP(glx_download(b.oc_cen.data(), b.cen, (size_t)m * d * 8, st, "knn_pass"));
+    GLX_HIP(hipStreamSynchronize(st));
+    b.oc_place = knn_chain_places(b.oc_cen, m, d);
+    std::vector<int64_t> fill(m + 1, 0);
+    for (int64_t i = 0; i < n; ++i) { b.oc_cid[i] = b.oc_place[b.oc_cid[i]]; ++fill[b.oc_cid[i] + 1]; }
+    for (int c = 0; c < m; ++c) fill[c + 1] += fill[c];
+    b.own_starts.assign(fill.begin(), fill.begin() + m);
+    b.oc_perm.resize(n);
+    for (int64_t i = 0; i < n; ++i) b.oc_perm[fill[b.oc_cid[i]]++] = (int)i;
+    GLX_UP(glx_upload(b.orig, b.oc_perm.data(), (size_t)n * 4, st, "knn_pass"));   // (no synchronisation behind it: b.oc_perm outlives the stream's work)
+    if (capture) capture->order.assign(b.oc_perm.begin(), b.oc_perm.end());
+    glx_pool_free(b.cen);                          // the cell pass allocates its own
+    b.cen = nullptr;
+    cell_starts = b.own_starts.data();
+    ncells = m;
+    return GLX_OK;
+  }
+
+  // centring in fp64 (distances are translation invariant; small norms keep the filter sharp), all of it on the device; then the
+  // buffers of the lists
+  int centre_and_alloc_lists() {
+    const int64_t nb_sum = (n + CENTRE_ROWS - 1) / CENTRE_ROWS, nb_max = (n + 255) / 256;
+    GLX_POOL(glx_pool_alloc((void**)&b.part, (size_t)std::max<int64_t>(nb_sum * d, nb_max) * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.rmax, 64));
+    int dt = 1;
+    while (dt < d && dt < 256) dt *= 2;
+    hipLaunchKernelGGL(knn_colsum_kernel, dim3((unsigned)nb_sum), dim3(256), 0, st, (const double*)b.X, n, d, dt, b.part);
+    GLX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(knn_mean_kernel, dim3(1), dim3(256), 0, st, (const double*)b.part, nb_sum, d, n, b.mean);
+    hipLaunchKernelGGL(knn_maxnorm_kernel, dim3((unsigned)nb_max), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean, n, d, b.part);
+    hipLaunchKernelGGL(knn_rmax_kernel, dim3(1), dim3(256), 0, st, (const double*)b.part, nb_max, b.rmax);
+    GLX_HIP(hipGetLastError());
+    // the candidate lists of a chunk of queries, the flags and thresholds of all, the lists that are returned
+    GLX_POOL(glx_pool_alloc((void**)&b.qnorm, (size_t)n * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.cand_d, (size_t)p.chunk * p.ncand * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.cand_i, (size_t)p.chunk * p.ncand * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.flags, (size_t)nq * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.dk2, (size_t)nq * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.nbad, 4));
+    GLX_HIP(hipMemsetAsync(b.nbad, 0, 4, st));
+    GLX_POOL(glx_pool_alloc((void**)&b.gtau, (size_t)nq * 4));
+    GLX_HIP(hipMemsetD32Async((hipDeviceptr_t)b.gtau, 0x7f800000, (size_t)nq, st));   // +inf: nothing published yet
+    GLX_POOL(glx_pool_alloc((void**)&b.rows, (size_t)nq * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.ind, (size_t)nq * k * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.dist, (size_t)nq * k * 8));
+    stamp("centred, norms bounded");
+    GLX_HIP(hipEventRecord(b.e0, st));
+    return GLX_OK;
+  }
+
+  // the filter's operand images; for rows that come in cells (bf16 filter, lists that can hold k: knn_seed_plan) the cell pruning
+  int prepare_operands() {
+    g_knn_stats[KS_CONCAT] = (double)p.cat;      // (0 on the fp32 filter, which has no concatenated form: not the previous search's value)
+    if (!p.use_bf16) {
+      GLX_POOL(glx_pool_alloc((void**)&b.Rf, (size_t)n * p.dpa * 4));
+      GLX_POOL(glx_pool_alloc((void**)&b.Qf, (size_t)n * p.dpa * 4));
+      hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean,
+                         n, d, p.dpa, b.Rf, b.Qf, b.qnorm);
+      GLX_HIP(hipGetLastError());
+      return GLX_OK;
+    }
+    GLX_POOL(glx_pool_alloc((void**)&b.Xb, (size_t)(n + KNN_PAD_ROWS) * 2 * p.dpa * 2));
+    GLX_POOL(glx_pool_alloc((void**)&b.nrm, (size_t)(n + KNN_PAD_ROWS) * 4));
+    if (p.cat) {
+      GLX_POOL(glx_pool_alloc((void**)&b.Xq, (size_t)(n + KNN_PAD_ROWS) * 64 * 2));
+      hipLaunchKernelGGL(knn_prep_bf16_cat_kernel, dim3((unsigned)((n + KNN_PAD_ROWS + 255) / 256)), dim3(256), 0, st, (const double*)b.X,
+                         (const double*)b.mean, n, d, b.Xb, b.Xq, b.nrm, b.qnorm, p.cat == 2 ? 1 : 0);
+    } else {
+      hipLaunchKernelGGL(knn_prep_bf16_kernel, dim3((unsigned)((n + KNN_PAD_ROWS + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean,
+                         n, d, p.dpa, b.Xb, b.nrm, b.qnorm);
+    }
+    GLX_HIP(hipGetLastError());
+    const KnnSeedPlan seed = knn_seed_plan(p, k, cell_starts ? ncells : 0);
+    g_knn_stats[KS_SEED_SAMPLE] = seed.seeded ? (double)seed.sub : 0.0;
+    g_knn_stats[KS_VISITED_SHARE] = 0.0;
+    g_knn_stats[KS_CELLS] = 0.0;
+    return seed.seeded ? seed_from_cells(seed.sub) : GLX_OK;
+  }
+
+  // the cell-pruned search: centres and radii of the cells, the seeding pre-pass over every seed_sub-th tile of a query block's own
+  // cells, the cells each block has to visit (knn_cellmask_kernel) as runs of tiles
+  int seed_from_cells(int seed_sub) {
+    const int64_t nqb = p.nqb;
+    GLX_POOL(glx_pool_alloc((void**)&b.cell_starts, (size_t)ncells * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.cen, (size_t)ncells * d * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.rad, (size_t)ncells * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.ub2, (size_t)nq * 8));
+    GLX_POOL(glx_pool_alloc((void**)&b.mask, (size_t)nqb * ncells));
+    GLX_POOL(glx_pool_alloc((void**)&b.nruns, (size_t)nqb * 4));
+    b.maxruns = ncells;
+    GLX_POOL(glx_pool_alloc((void**)&b.runs, (size_t)nqb * 2 * ncells * 4));   // (from here on the tile launches follow the runs)
+    GLX_UP(glx_upload(b.cell_starts, cell_starts, (size_t)ncells * 8, st, "knn_pass"));
+    // centres and radii of the cells
+    GLX_POOL(glx_pool_alloc((void**)&b.cpart, (size_t)ncells * CELL_SPLIT * (d + 1) * 8));
+    double* prad = b.cpart + (size_t)ncells * CELL_SPLIT * d;
+    hipLaunchKernelGGL(knn_cell_sum_kernel, dim3((unsigned)ncells, CELL_SPLIT), dim3(256), 0, st, (const double*)b.X, d, (const int64_t*)b.cell_starts, n,
+                       ncells, b.cpart);
+    hipLaunchKernelGGL(knn_cell_centre_kernel, dim3((unsigned)ncells), dim3(256), 0, st, (const double*)b.cpart, d, (const int64_t*)b.cell_starts, n, ncells,
+                       b.cen);
+    hipLaunchKernelGGL(knn_cell_rad_kernel, dim3((unsigned)ncells, CELL_SPLIT), dim3(256), (size_t)(d + 256) * 8, st, (const double*)b.X, d,
+                       (const int64_t*)b.cell_starts, n, ncells, (const double*)b.cen, prad);
+    hipLaunchKernelGGL(knn_cell_radfin_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, (const double*)prad,
+                       (const int64_t*)b.cell_starts, n, ncells, b.rad);
+    hipLaunchKernelGGL(knn_runs_kernel, dim3((unsigned)((nqb + 255) / 256)), dim3(256), 0, st, (const unsigned char*)nullptr,
+                       (const int64_t*)b.cell_starts, n, ncells, p.BR, q0, q1, nqb, b.maxruns, b.runs, b.nruns, (unsigned long long*)nullptr);
+    GLX_HIP(hipGetLastError());
+    GLX_POOL(glx_pool_alloc((void**)&b.pre_d, (size_t)nq * 2 * p.KP * 4));
+    GLX_POOL(glx_pool_alloc((void**)&b.pre_i, (size_t)nq * 2 * p.KP * 4));
+    GLX_UP(knn_launch_tile_bf16(p.KP, p.NKB, b, n, q0, q1, seed_sub, st, p.cat, true));
+    GLX_UP(knn_launch_seed(p.KP, b, nq, q0, k, p.cerr, st));
+    hipLaunchKernelGGL(knn_cellmask_kernel, dim3((unsigned)nqb), dim3(256), (size_t)16 * d * 8, st, (const double*)b.X, d, q0, q1, (const double*)b.cen,
+                       (const double*)b.rad, ncells, (const double*)b.ub2, b.mask);
+    GLX_POOL(glx_pool_alloc((void**)&b.visited, 8));
+    GLX_HIP(hipMemsetAsync(b.visited, 0, 8, st));
+    hipLaunchKernelGGL(knn_runs_kernel, dim3((unsigned)((nqb + 255) / 256)), dim3(256), 0, st, (const unsigned char*)b.mask,
+                       (const int64_t*)b.cell_starts, n, ncells, p.BR, q0, q1, nqb, b.maxruns, b.runs, b.nruns, b.visited);
+    GLX_HIP(hipGetLastError());
+    g_knn_stats[KS_CELLS] = (double)ncells;
+    return GLX_OK;
+  }
+
+  // filter + re-rank, in one go or (wide) chunk by chunk
+  int filter_and_rerank() {
+    if (!p.wide) {
+      GLX_UP(launch_tile(q0, q1));
+      GLX_HIP(hipEventRecord(b.e1, st));
+      GLX_UP(knn_launch_rerank(b, n, d, k, q0, nq, p.lists, p.KP, p.M, p.cerr, st));
+      GLX_HIP(hipEventRecord(b.e2, st));
+      return GLX_OK;
+    }
+    // chunk by chunk: filter, re-rank (flags, dk2 and the flagged rows are numbered within the pass, the lists go to their final rows).
+    // Every chunk's stage boundaries have events of their own, read once the stream has drained: the host never waits between chunks.
+    hipEvent_t start = b.e0;
+    for (int64_t c0 = q0; c0 < q1; c0 += p.chunk) {
+      const int64_t c1 = std::min(q1, c0 + p.chunk);
+      if (c0 > q0) GLX_HIP(hipMemsetD32Async((hipDeviceptr_t)b.gtau, 0x7f800000, (size_t)(c1 - c0), st));   // (the filter's thresholds are per chunk row)
+      GLX_UP(launch_tile(c0, c1));
+      hipEvent_t et = b.e1, er = b.e2;                 // (the last chunk ends on the pass's own events: the fallback is timed from e2)
+      if (c1 < q1) {
+        GLX_HIP(hipEventCreate(&et));
+        b.chunk_ev.push_back(et);
+        GLX_HIP(hipEventCreate(&er));
+        b.chunk_ev.push_back(er);
+      }
+      GLX_HIP(hipEventRecord(et, st));
+      GLX_UP(knn_launch_rerank_wide(b, n, d, k, q0, c0, c1 - c0, p.lists, p.KP, p.M, p.cerr, st));
+      GLX_HIP(hipEventRecord(er, st));
+      b.chunk_marks.push_back({start, et, er});
+      start = er;
+    }
+    return GLX_OK;
+  }
+
+  // the host's look at the pass: rows that failed the acceptance test, the centring pass's verdict on the input, the pruning's share;
+  // KNN_ESCALATE if repairing the failed rows one by one would cost more than searching again with the long lists
+  int host_look() {
+    GLX_HIP(hipMemcpyAsync(&h_nbad, b.nbad, 4, hipMemcpyDeviceToHost, st));
+    GLX_HIP(hipMemcpyAsync(h_rmax, b.rmax, 8, hipMemcpyDeviceToHost, st));
+    if (b.visited) GLX_HIP(hipMemcpyAsync(&h_visited, b.visited, 8, hipMemcpyDeviceToHost, st));
+    GLX_HIP(hipStreamSynchronize(st));
+    if (b.visited) {
+      g_knn_stats[KS_VISITED_SHARE] = (double)h_visited / ((double)p.nqb * (double)p.ntiles);
+      if (stamp.on) fprintf(stderr, "[glx] knn: cell pruning, %d cells: %.1f %% of the (query block, ref tile) pairs visited\n", ncells, 100.0 * g_knn_stats[KS_VISITED_SHARE]);
+    }
+    stamp("tile + re-rank done, flags on the host");
+    GLX_CHECK(h_rmax[1] == 1.0f, GLX_EINVAL, "glx_knn_bruteforce: non-finite input");   // (the first host look at the centring pass)
+    nbad = (size_t)h_nbad;
+    if (knn_should_escalate(p, n, d, k, nq, nbad, b.visited ? g_knn_stats[KS_VISITED_SHARE] : 1.0)) {
+      g_knn_stats[KS_FALLBACK_ROWS] = (double)nbad;
+      return KNN_ESCALATE;
+    }
+    return GLX_OK;
+  }
+
+  // the rows that failed the acceptance test redone exactly
+  int fallback() {
+    const size_t nr = nbad;
+    if (nr && p.wide) {
+      const KnnWideFallbackPlan f = knn_wide_fallback_plan(k, nr);
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_pd, f.batch * FB_SPLIT * k * 8));
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_pi, f.batch * FB_SPLIT * k * 4));
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_cnt, f.batch * 2 * 4));
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_bd, f.batch * f.cap * 8));
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_bi, f.batch * f.cap * 4));
+      for (size_t r0 = 0; r0 < nr; r0 += f.batch) GLX_UP(knn_launch_fallback_wide(b, n, d, k, q0, b.rows + r0, std::min(f.batch, nr - r0), f.cap, st));
+    } else if (nr) {
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_pd, nr * FB_SPLIT * k * 8));
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_pi, nr * FB_SPLIT * k * 4));
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_cnt, nr * 2 * 4));            // [nr] counts, [nr] redo marks
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_bd, nr * FB_CAP * 8));
+      GLX_POOL(glx_pool_alloc((void**)&b.fb_bi, nr * FB_CAP * 4));
+      GLX_HIP(hipMemsetAsync(b.fb_cnt, 0, nr * 2 * 4, st));
+      const int* fb_runs = (const int*)(b.visited ? b.runs : nullptr);   // (b.runs: the main pass's runs when the search was cell-pruned -- the pre-pass's were overwritten by them)
+      GLX_UP(knn_launch_fallback(b, n, d, k, q0, nr, fb_runs, p.BR, st));
+    }
+    GLX_HIP(hipEventRecord(b.e3, st));
+    return GLX_OK;
+  }
+
+  // the lists to the caller's arrays, or (capture) handed to the result object together with the cell order; the statistics
+  int finish() {
+    if (ind_out) GLX_UP(glx_download(ind_out, b.ind, (size_t)nq * k * 8, st, "knn_pass"));
+    if (dist_out) GLX_UP(glx_download(dist_out, b.dist, (size_t)nq * k * 8, st, "knn_pass"));
+    GLX_HIP(hipStreamSynchronize(st));
+    stamp("results on the host");
+    if (perm_pending) {    // the permutation stays on the device with the result (glx_knn_result_order copies it into the caller's --
+      glx_pool_free(capture->order_dev);      // page-locked -- array: a synchronous copy into fresh pageable memory cost 8 ms here)
+      capture->order_dev = b.orig;
+      b.orig = nullptr;
+    }
+    if (capture) {         // the lists stay on the device with the caller's result object (everything that writes them has finished)
+      glx_pool_free(capture->ind);
+      glx_pool_free(capture->dist);
+      capture->ind = b.ind;
+      capture->dist = b.dist;
+      capture->n = n;
+      capture->k = k;
+      capture->device = device;
+      b.ind = nullptr;
+      b.dist = nullptr;
+    }
+    float ms_tile = 0, ms_rr = 0, ms_fb = 0;
+    GLX_HIP(hipEventElapsedTime(&ms_tile, b.e0, b.e1));
+    GLX_HIP(hipEventElapsedTime(&ms_rr, b.e1, b.e2));
+    GLX_HIP(hipEventElapsedTime(&ms_fb, b.e2, b.e3));
+    if (p.wide) {                // (the sum over the chunks; a later chunk's filter time includes the reset of the thresholds)
+      ms_tile = ms_rr = 0;
+      for (const auto& m : b.chunk_marks) {
+        float t = 0, r = 0;
+        GLX_HIP(hipEventElapsedTime(&t, m[0], m[1]));
+        GLX_HIP(hipEventElapsedTime(&r, m[1], m[2]));
+        ms_tile += t;
+        ms_rr += r;
+      }
+    }
+    g_knn_stats[KS_TILE_MS] = ms_tile;
+    g_knn_stats[KS_RERANK_MS] = ms_rr;
+    g_knn_stats[KS_FALLBACK_ROWS] = (double)nbad;
+    g_knn_stats[KS_TOTAL_MS] = ms_tile + ms_rr + ms_fb;
+    g_knn_stats[KS_FALLBACK_MS] = ms_fb;
+    g_knn_stats[KS_DPA] = (double)p.dpa;
+    g_knn_stats[KS_NSPLIT] = (double)p.nsplit;
+    g_knn_stats[KS_KP] = p.use_bf16 ? -(double)p.KP : (double)p.KP;
+    g_knn_stats[KS_CHUNKS] = (double)p.nchunks;
+    g_knn_stats[KS_WIDE] = p.wide ? 1.0 : 0.0;
+    g_knn_stats[KS_CANDIDATES] = (double)p.ncand;
+    return GLX_OK;
+  }
+};
 // One pass of the search.  long_lists = false: the default (short lists where they apply); if then so many query rows fail
 // the acceptance test that repairing them row by row -- each streams the whole data set -- would take longer than
 // searching again, KNN_ESCALATE is returned: the caller repeats the search with the long lists (one list
@@ -115,498 +503,34 @@ static const int KNN_ESCALATE = 1;    // knn_pass: too many rows failed the acce
 // the pass worked out (if it did), instead of being copied out.
 static int knn_pass(const double* X, int64_t n, int d, int k, int64_t q0, int64_t q1, int64_t* ind_out, double* dist_out, int device,
                     bool long_lists, glx_knn_result* capture, const int64_t* cell_starts = nullptr, int ncells = 0, int auto_cells = 0) {
-  GLX_CHECK(X && ((ind_out && dist_out) || capture), GLX_EINVAL, "glx_knn_bruteforce: null argument");
-  GLX_CHECK(!capture || (q0 == 0 && q1 == n), GLX_EINVAL, "glx_knn_search: a result object holds a full search");
-  GLX_CHECK(n >= 1 && d >= 1 && k >= 1, GLX_EINVAL, "glx_knn_bruteforce: need n, d, k >= 1 (n=%lld d=%d k=%d)", (long long)n, d, k);
-  GLX_CHECK(k <= n, GLX_EINVAL, "glx_knn_bruteforce: k=%d exceeds the number of points %lld", k, (long long)n);
-  GLX_CHECK(n < (1ll << 31) - BR_MAX, GLX_EINVAL, "glx_knn_bruteforce: n must fit int32");
-  GLX_CHECK(0 <= q0 && q0 <= q1 && q1 <= n, GLX_EINVAL, "glx_knn_bruteforce: bad query range");
-  GLX_CHECK(k <= KNN_K_MAX, GLX_EUNSUPPORTED, "glx_knn_search: k=%d (incl. self) above the supported %d", k, KNN_K_MAX);
-  GLX_CHECK(d <= 16382, GLX_EUNSUPPORTED, "glx_knn_bruteforce: d=%d above the supported 16382", d);
+  GLX_UP(knn_check_args(X, n, d, k, q0, q1, ind_out, dist_out, capture));
   const int64_t nq = q1 - q0;
   if (nq == 0) return GLX_OK;
-  const bool timing = getenv("GLX_TIMING") != nullptr;
-  const auto t_host0 = std::chrono::steady_clock::now();
-  auto stamp = [&](const char* what) {
-    if (timing) fprintf(stderr, "[glx] knn: %-28s %.2f ms since the call\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count());
-  };
+  const KnnStamp stamp = {getenv("GLX_TIMING") != nullptr, std::chrono::steady_clock::now()};
   GLX_HIP(hipSetDevice(device));
-  // d + 2 <= 132: the query's features stay in registers; above that the feature dimension is blocked
-  int KP = k <= 12 ? 16 : (k <= 28 ? 32 : 64);
-  // Short lists.  A query's candidates are kept in 2*nsplit separate lists (two half-wavefronts x
-  // nsplit ref ranges); with >= 8 lists, 8 entries per list hold the k <= 12 nearest unless 8 of
-  // them fall into the same list (5e-5 per query for k = 11; the acceptance test of the re-rank
-  // sees a full list whose threshold is too small and sends the row to the exact fallback).  The
-  // shorter lists free LDS for a third workgroup per CU and halve the list rescans: 5.1 -> 3.6 ms
-  // at config 2, 94 -> 108 TFLOP/s at d = 64.  Not for the blocked variant: at large d the fp32
-  // error margin of the acceptance test makes short lists fall back too often.
-  // The same argument one size up: 16 entries for k <= 28 (3e-7 per query at k = 28), 32 for k <= 60.
-  const bool short_lists = !long_lists && d + 2 <= 132 && g_knn_opt.lists != 2;
-  if (short_lists) KP = k <= 12 ? 8 : (k <= 28 ? 16 : 32);
-  // The wide plan (k > 60): lists of 32 wherever the short lists apply (d + 2 <= 132: the split-bf16 filter for d <= 128, the
-  // fp32-input one for d = 129, 130), of 64 (the fp32-input filter) for the long lists and d > 130; ref ranges such that the
-  // 2 nsplit lists hold about 4 k candidates (below)
-  const bool wide = k > KNN_K_NARROW;
-  if (wide) KP = short_lists ? 32 : 64;
-  int DH = knn_kb(KP), nkb = 1;
-  if (d + 2 <= 132 && !(KP == 64 && d + 2 > 36)) {   // (KP = 64 lists + a wide double-buffered tile exceed the LDS)
-    for (int cand : {8, 12, 18, 34, 66})
-      if (2 * cand >= d + 2) { DH = cand; break; }
-  } else {
-    nkb = (d + 2 + 2 * DH - 1) / (2 * DH);
-  }
-  // Filter arithmetic.  Default: split-bf16 operands on the bf16 matrix cores (d <= 128 with the short lists); the fp32-input
-  // MFMA kernel serves everything else (and glx_knn_options::filter = 2).
-  const bool use_bf16 = short_lists && d <= 128 && KP <= 32 && g_knn_opt.filter != 2;
-  int NKB = 0;
-  if (use_bf16) {
-    for (int cand : {1, 2, 4, 6, 8})
-      if (16 * cand >= d) { NKB = cand; break; }
-  }
-  const int dpa = use_bf16 ? 16 * NKB : 2 * DH * nkb;
-  const int64_t nqb = (nq + BQ - 1) / BQ;
-  const int BR = use_bf16 ? 32 * bf16_nsub(NKB, KP) : 32 * tile_nsub(DH, KP);
-  const int64_t ntiles = (n + BR - 1) / BR;
-  int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, ntiles), (1024 + nqb - 1) / nqb));
-  if (short_lists) {
-    // >= 8 lists per query; 16 for the 8-entry lists once the data no longer sits in cache (an exact
-    // fallback row then streams all of X k times: 329 rows cost 0.6 s at n = 2e6 -- with 16 lists 5 rows are left)
-    const int64_t want = (KP == 8 && (double)n * d * 8.0 > 64.0 * 1024 * 1024) ? 8 : 4;
-    nsplit = (int)std::max<int64_t>(nsplit, std::min<int64_t>(want, ntiles));
-  }
-  if (g_knn_opt.nsplit > 0) nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, ntiles), g_knn_opt.nsplit));
-  if (wide) {
-    // 2 nsplit lists of KP, nsplit a power of two in [8, 32] (or the number of ref tiles when there are fewer: n = 257 gives 9):
-    // lists * KP >= 4 k where 32 ranges allow it (k <= 128 with 32 entries: 16 lists, 512 candidates; k = 1024 with 64 entries:
-    // 64 lists).  A query's k nearest then fill a list to a quarter on average,
-    // and the smallest full list's threshold lies well beyond the k-th distance.  Above k = 512 the 64 lists of 32 hold 2 k: half
-    // full on average, 1.9 % of config 2's rows go to the fallback at k = 1024 -- and the search takes half the time of the fp32
-    // filter's 64 lists of 64 (34 vs 65 ms of kernels, profiles/knn_wide_k.txt).  With fewer tiles than that (n < 32 nsplit)
-    // every range is one tile of 32 refs, whose half of 16 fits any list: all refs are candidates.  An override never goes below
-    // k candidates.
-    int want = 8;
-    while (want < 32 && 2 * want * KP < 4 * k) want *= 2;
-    if (g_knn_opt.nsplit > 0) want = std::max(g_knn_opt.nsplit, (k + 2 * KP - 1) / (2 * KP));
-    nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, ntiles), want));
-  }
-  const int lists = nsplit * 2;
-  const int ncand = lists * KP;
-  int M = 64;
-  while (M < ncand) M *= 2;
-  // wide: the queries in chunks whose candidates (8 bytes each) stay within a fixed budget -- 2.3 GB at 70 000 rows x 4096
-  // candidates otherwise, 33 GB at 10^6; the lists of k <= 60 are short enough to be held for all queries at once
-  const int64_t chunk = wide ? std::min<int64_t>(nq, std::max<int64_t>(BQ, (int64_t)((KNN_CAND_BUDGET / ((size_t)ncand * 8)) / BQ * BQ))) : nq;
-  const int64_t nchunks = (nq + chunk - 1) / chunk;
-
-  // (host buffers of the cell order: declared in front of `b`, whose destructor drains the stream they are filled through)
-  std::vector<int> oc_sample, oc_cid, oc_perm, oc_place;
-  // the wide plan's timing events of the chunks before the last (destroyed after `b`'s destructor has drained the stream)
-  struct ChunkEvents {
-    std::vector<hipEvent_t> ev;
-    ~ChunkEvents() { for (hipEvent_t e : ev) hipEventDestroy(e); }
-  } chunk_ev;
-  std::vector<std::array<hipEvent_t, 3>> chunk_marks;   // per chunk: start, filter done, re-rank done
-  std::vector<double> oc_cen;
-  KnnBufs b;
-  {
-    int rcw = glx_work_acquire(device, &b.work);
-    if (rcw) return rcw;
-  }
-  b.stream = b.work->stream;
-  b.e0 = b.work->ev[0]; b.e1 = b.work->ev[1]; b.e2 = b.work->ev[2]; b.e3 = b.work->ev[3];
-  hipStream_t st = b.stream;
-  GLX_POOL(glx_pool_alloc((void**)&b.X, (size_t)n * d * 8));
-  GLX_POOL(glx_pool_alloc((void**)&b.mean, d * 8));
-  stamp("stream, events, buffers");
-  int rc0 = GLX_OK;
-  // (hipMemcpyDefault: X may also be a DEVICE pointer -- glx_knn_bruteforce_range / glx_knn_cells_range of the sharded build, whose
-  // features are generated, ordered and kept on the GPU; the library-formed cells below read sample rows on the host and need a host X)
-  bool on_host = true;
-  {
-    hipPointerAttribute_t at;
-    on_host = hipPointerGetAttributes(&at, X) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged);
-    (void)hipGetLastError();
-  }
-  if (on_host) {
-    // the caller's (pageable) array goes up through the library's page-locked staging area, checked (glx_internal.h: why)
-    rc0 = glx_upload(b.X, X, (size_t)n * d * 8, st, "features of a search");
-    if (rc0) return rc0;
-  } else {
-    GLX_HIP(hipMemcpyAsync(b.X, X, (size_t)n * d * 8, hipMemcpyDefault, st));
-  }
-  stamp("X enqueued");
-  if (g_debug_flags & 1) {
-    if (on_host) {
-      const int rcv = knn_verify_upload(X, b.X, n, d, st, "after the upload");
-      if (rcv) return rcv;
-    }
-  }
-  // Cells formed by the library (auto_cells).  > 1: that many cells (nearest of evenly spaced sample rows), the rows reordered by
-  // cell and searched with the cell pruning of glx_knn_cells_range; the re-rank ranks by and returns the caller's indices.
-  // < -1 (below the size where pruning pays): the rows ARE reordered by -auto_cells chained cells on the device and then searched
-  // all pairs.  The 32 queries of a wavefront then come from one corner of feature space, a ref tile holds candidates for many of
-  // them or for none, and fewer wave-tiles leave the tile kernel's fast path: config 2 2.06 -> 1.83 ms of search wall time, config
-  // 3's shape 3.06 -> 2.63 ms, data without clusters unchanged (profiles/r03_knn_cells_midsize.txt).
-  std::vector<int64_t> own_starts;
-  const bool reorder_only = auto_cells < -1;
-  if (auto_cells < -1) auto_cells = -auto_cells;
-  // the cells in a chain of nearest centres (greedy, from the centre farthest from the centres' mean): neighbouring cells of
-  // feature space end up next to each other in the row order, which then serves as a locality order for the graph's operators
-  // too (one XCD's share of the rows = a few whole clusters; with the cells in arbitrary order the sweep at 10^6 rows ran 20 % slower);
-  // then the rows by cell (counting sort, ascending caller index inside a cell).  Host work on oc_cid / oc_cen.
-  auto chain_places = [&](const std::vector<double>& cen, int m) -> std::vector<int> {
-    std::vector<double> mean(d, 0.0);
-    for (int c = 0; c < m; ++c)
-      for (int f = 0; f < d; ++f) mean[f] += cen[(size_t)c * d + f] / m;
-    const int cfs = (d + 31) / 32;       // (every cfs-th feature, as in the assignment: m^2 d flops on one host thread otherwise)
-    auto dist2 = [&](const double* a, const double* bb) { double t = 0; for (int f = 0; f < d; f += cfs) { const double q = a[f] - bb[f]; t += q * q; } return t; };
-    int cur = 0;
-    double far = -1.0;
-    for (int c = 0; c < m; ++c) { const double t = dist2(&cen[(size_t)c * d], mean.data()); if (t > far) { far = t; cur = c; } }
-    std::vector<int> place(m, -1);
-    for (int pos = 0; pos < m; ++pos) {
-      place[cur] = pos;
-      int nxt = -1;
-      double best = INFINITY;
-      for (int c = 0; c < m; ++c)
-        if (place[c] < 0) { const double t = dist2(&cen[(size_t)c * d], &cen[(size_t)cur * d]); if (t < best) { best = t; nxt = c; } }
-      if (nxt < 0) break;
-      cur = nxt;
-    }
-    return place;
-  };
-  bool perm_pending = false;
-  if (auto_cells > 1 && q0 == 0 && q1 == n && !long_lists && d <= 128 && n >= 4 * (int64_t)auto_cells) {
-    const int m = auto_cells;
-    oc_sample.resize(m);
-    for (int c = 0; c < m; ++c) oc_sample[c] = (int)(((2 * (int64_t)c + 1) * n) / (2 * (int64_t)m));     // evenly spaced rows
-    GLX_POOL(glx_pool_alloc((void**)&b.cen, (size_t)m * d * 8));
-    GLX_POOL(glx_pool_alloc((void**)&b.cell_id, (size_t)std::max<int64_t>(n, m) * 4));
-    GLX_UP(glx_upload(b.cell_id, oc_sample.data(), (size_t)m * 4, st, __func__));
-    hipLaunchKernelGGL(knn_gather_rows_kernel, dim3((unsigned)(((int64_t)m * d + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const int*)b.cell_id,
-                       (int64_t)m, d, b.cen);
-    hipLaunchKernelGGL(knn_assign_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), (size_t)16 * d * 8, st, (const double*)b.X, d, n, (const double*)b.cen, m,
-                       b.cell_id, (d + 31) / 32);
-    GLX_HIP(hipGetLastError());
-    GLX_POOL(glx_pool_alloc((void**)&b.orig, (size_t)n * 4));
-    if (reorder_only) {
-      // the chain of the cells from the caller's copy of the sample rows (the same doubles the device gathered), the rows into cell
-      // order by the three knn_cellrank kernels: nothing here waits for the device
-      oc_cen.resize((size_t)m * d);
-      for (int c = 0; c < m; ++c) memcpy(&oc_cen[(size_t)c * d], X + (size_t)oc_sample[c] * d, (size_t)d * 8);
-      oc_place = chain_places(oc_cen, m);
-      const int nb = (int)((n + 255) / 256);
-      GLX_POOL(glx_pool_alloc((void**)&b.place, (size_t)m * 4));
-      GLX_POOL(glx_pool_alloc((void**)&b.bh, (size_t)(nb + 1) * m * 4));     // (+ one row: the keys' totals / starting positions)
-      GLX_UP(glx_upload(b.place, oc_place.data(), (size_t)m * 4, st, __func__));
-      hipLaunchKernelGGL(knn_cellrank_hist_kernel, dim3((unsigned)nb), dim3(256), (size_t)m * 4, st, b.cell_id, (const int*)b.place, n, m, b.bh);
-      hipLaunchKernelGGL(knn_cellrank_scan_kernel, dim3((unsigned)m), dim3(256), 0, st, b.bh, nb, m);
-      hipLaunchKernelGGL(knn_cellrank_base_kernel, dim3(1), dim3(256), 0, st, b.bh, nb, m);
-      hipLaunchKernelGGL(knn_cellrank_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const int*)b.cell_id, n, m, (const int*)b.bh, nb, b.orig);
-      perm_pending = capture != nullptr;               // the permutation comes back with the results (glx_knn_result_order)
-    } else {
-      // the pruned search needs the cells' extents on the host: cell ids and centres come back, the rows are counted into chained
-      // cells here (stable: ascending caller index inside a cell)
-      oc_cid.resize(n);
-      oc_cen.resize((size_t)m * d);
-      GLX_UP(glx_download(oc_cid.data(), b.cell_id, (size_t)n * 4, st, __func__));
-      GLX_UP(glx_download(oc_cen.data(), b.cen, (size_t)m * d * 8, st, __func__));
-      GLX_HIP(hipStreamSynchronize(st));
-      oc_place = chain_places(oc_cen, m);
-      std::vector<int64_t> fill(m + 1, 0);
-      for (int64_t i = 0; i < n; ++i) { oc_cid[i] = oc_place[oc_cid[i]]; ++fill[oc_cid[i] + 1]; }
-      for (int c = 0; c < m; ++c) fill[c + 1] += fill[c];
-      own_starts.assign(fill.begin(), fill.begin() + m);
-      oc_perm.resize(n);
-      for (int64_t i = 0; i < n; ++i) oc_perm[fill[oc_cid[i]]++] = (int)i;
-      // (no synchronisation behind the upload: oc_perm outlives the stream's work -- see its declaration)
-      GLX_UP(glx_upload(b.orig, oc_perm.data(), (size_t)n * 4, st, __func__));
-      if (capture) capture->order.assign(oc_perm.begin(), oc_perm.end());
-      glx_pool_free(b.cen);                          // the cell pass allocates its own
-      b.cen = nullptr;
-      cell_starts = own_starts.data();
-      ncells = m;
-    }
-    b.Xraw = b.X;
-    b.X = nullptr;
-    GLX_POOL(glx_pool_alloc((void**)&b.X, (size_t)n * d * 8));
-    hipLaunchKernelGGL(knn_gather_rows_kernel, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, st, (const double*)b.Xraw, (const int*)b.orig, n, d, b.X);
-    GLX_HIP(hipGetLastError());
-    stamp("rows reordered by cell");
-  }
-  // centring in fp64 (distances are translation invariant; small norms keep the filter sharp), all of it on the device
-  const int64_t nb_sum = (n + CENTRE_ROWS - 1) / CENTRE_ROWS, nb_max = (n + 255) / 256;
-  GLX_POOL(glx_pool_alloc((void**)&b.part, (size_t)std::max<int64_t>(nb_sum * d, nb_max) * 8));
-  GLX_POOL(glx_pool_alloc((void**)&b.rmax, 64));
-  {
-    int dt = 1;
-    while (dt < d && dt < 256) dt *= 2;
-    hipLaunchKernelGGL(knn_colsum_kernel, dim3((unsigned)nb_sum), dim3(256), 0, st, (const double*)b.X, n, d, dt, b.part);
-    GLX_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(knn_mean_kernel, dim3(1), dim3(256), 0, st, (const double*)b.part, nb_sum, d, n, b.mean);
-  hipLaunchKernelGGL(knn_maxnorm_kernel, dim3((unsigned)nb_max), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean, n, d, b.part);
-  hipLaunchKernelGGL(knn_rmax_kernel, dim3(1), dim3(256), 0, st, (const double*)b.part, nb_max, b.rmax);
-  GLX_HIP(hipGetLastError());
-  // |filter value - exact dist^2| <= cerr * (|q| + rmax)^2.
-  // fp32 filter: input rounding (2^-24 per coordinate), dpa products and sums at 2^-24 each, norms computed in fp32; generous constant.
-  // bf16 filter: eps = cerr (|q| + rmax)^2 with cerr ~ 2^-16.  The dropped parts of the split products (lo.lo and the residuals of the
-  // two roundings) are <= 3.1 * 2^-16 |q||r| in q.r in the worst case -- every coordinate's errors at their bounds and aligned --, twice
-  // that in the distance, i.e. <= 1.55 * 2^-16 (|q| + rmax)^2; plus 3 kpad fp32 accumulations, fp32 norms and input rounding (the second
-  // term, doubled: the matrix pipe's internal rounding mode is not documented).  So |filter - exact| < 2 eps ALWAYS, which is what the
-  // acceptance test of the re-rank needs (it asks for a margin of 2 eps), and <= 0.52 eps on every pair of the randomised suite's inputs
-  // (an emulation of the split arithmetic: profiles/r05_knn_tile_pmc.txt); the re-rank's fp32 screen allows for 2 eps per value as well.
-  const double cerr = use_bf16 ? 2.0 * (std::ldexp(1.0, -17) + (1.5 * (3.0 * dpa + 4.0) + d + 16.0) * std::ldexp(1.0, -24))
-                               : (double)(dpa + 8) * std::ldexp(1.0, -22);
-  GLX_POOL(glx_pool_alloc((void**)&b.qnorm, (size_t)n * 4));
-  GLX_POOL(glx_pool_alloc((void**)&b.cand_d, (size_t)chunk * ncand * 4));
-  GLX_POOL(glx_pool_alloc((void**)&b.cand_i, (size_t)chunk * ncand * 4));
-  GLX_POOL(glx_pool_alloc((void**)&b.flags, (size_t)nq * 4));
-  GLX_POOL(glx_pool_alloc((void**)&b.dk2, (size_t)nq * 8));
-  GLX_POOL(glx_pool_alloc((void**)&b.nbad, 4));
-  GLX_HIP(hipMemsetAsync(b.nbad, 0, 4, st));
-  GLX_POOL(glx_pool_alloc((void**)&b.gtau, (size_t)nq * 4));
-  GLX_HIP(hipMemsetD32Async((hipDeviceptr_t)b.gtau, 0x7f800000, (size_t)nq, st));   // +inf: nothing published yet
-  GLX_POOL(glx_pool_alloc((void**)&b.rows, (size_t)nq * 4));
-  GLX_POOL(glx_pool_alloc((void**)&b.ind, (size_t)nq * k * 8));
-  GLX_POOL(glx_pool_alloc((void**)&b.dist, (size_t)nq * k * 8));
-  stamp("centred, norms bounded");
-  GLX_HIP(hipEventRecord(b.e0, st));
-  int rc;
-  int cat = 0;
-  g_knn_stats[9] = 0.0;      // (the fp32 filter has no concatenated form: not the previous search's value)
-  if (use_bf16) {
-    // 17 <= d <= 21 (two blocks of 16 per half): the three split products as ONE contraction over concatenated operands,
-    // 4 MFMAs per 32 x 32 tile instead of 6 (d <= 16 needs 3 either way)
-    // ... and for d <= 20 with the norm folded in (glx_knn_options::concat = 1: without the fold, 0: blocks of 16 features)
-    cat = (d <= KNN_CAT_SEG && NKB == 2) ? (d < KNN_CAT_SEG ? 2 : 1) : 0;
-    if (g_knn_opt.concat >= 0) cat = std::min(cat, g_knn_opt.concat);
-    GLX_POOL(glx_pool_alloc((void**)&b.Xb, (size_t)(n + KNN_PAD_ROWS) * 2 * dpa * 2));
-    GLX_POOL(glx_pool_alloc((void**)&b.nrm, (size_t)(n + KNN_PAD_ROWS) * 4));
-    if (cat) {
-      GLX_POOL(glx_pool_alloc((void**)&b.Xq, (size_t)(n + KNN_PAD_ROWS) * 64 * 2));
-      hipLaunchKernelGGL(knn_prep_bf16_cat_kernel, dim3((unsigned)((n + KNN_PAD_ROWS + 255) / 256)), dim3(256), 0, st, (const double*)b.X,
-                         (const double*)b.mean, n, d, b.Xb, b.Xq, b.nrm, b.qnorm, cat == 2 ? 1 : 0);
-    } else {
-      hipLaunchKernelGGL(knn_prep_bf16_kernel, dim3((unsigned)((n + KNN_PAD_ROWS + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean,
-                         n, d, dpa, b.Xb, b.nrm, b.qnorm);
-    }
-    GLX_HIP(hipGetLastError());
-    g_knn_stats[9] = (double)cat;
-    // The seeding pre-pass (knn_seed_kernel) runs the tile kernel over a sample of the refs first and starts every list of the
-    // search proper at a threshold derived from it.  Over all refs it does not pay (measured, profiles/r03_knn_seed.txt: the k-th
-    // of a 1/8 sample is the 8k-th of the whole set, 79 % of the wave-tiles still hold a candidate and the pre-pass costs its
-    // eighth); the cell-pruned search needs it: its bound ub2 decides which cells a query block visits.
-    const bool cells = cell_starts != nullptr && ncells > 1;
-    // sample the block's own cells: every tile of small cells, every 8th of cells of >= 128 tiles
-    const int seed_sub = cells ? (int)std::max<int64_t>(1, std::min<int64_t>(8, std::max<int64_t>(1, ntiles / ncells) / 16)) : 0;
-    // (not for the wide plan: its lists hold a fraction of k each, and the search stays all pairs -- on the reordered rows if any)
-    const bool seeded = cells && 2 * KP >= k && !wide;
-    g_knn_stats[10] = seeded ? (double)seed_sub : 0.0;
-    g_knn_stats[11] = 0.0;
-    g_knn_stats[12] = 0.0;
-    if (seeded) {
-      GLX_POOL(glx_pool_alloc((void**)&b.cell_starts, (size_t)ncells * 8));
-      GLX_POOL(glx_pool_alloc((void**)&b.cen, (size_t)ncells * d * 8));
-      GLX_POOL(glx_pool_alloc((void**)&b.rad, (size_t)ncells * 8));
-      GLX_POOL(glx_pool_alloc((void**)&b.ub2, (size_t)nq * 8));
-      GLX_POOL(glx_pool_alloc((void**)&b.mask, (size_t)nqb * ncells));
-      GLX_POOL(glx_pool_alloc((void**)&b.nruns, (size_t)nqb * 4));
-      b.maxruns = ncells;
-      GLX_POOL(glx_pool_alloc((void**)&b.runs, (size_t)nqb * 2 * ncells * 4));   // (from here on the tile launches follow the runs)
-      GLX_UP(glx_upload(b.cell_starts, cell_starts, (size_t)ncells * 8, st, __func__));
-      // centres and radii of the cells
-      GLX_POOL(glx_pool_alloc((void**)&b.cpart, (size_t)ncells * CELL_SPLIT * (d + 1) * 8));
-      double* prad = b.cpart + (size_t)ncells * CELL_SPLIT * d;
-      hipLaunchKernelGGL(knn_cell_sum_kernel, dim3((unsigned)ncells, CELL_SPLIT), dim3(256), 0, st, (const double*)b.X, d, (const int64_t*)b.cell_starts, n,
-                         ncells, b.cpart);
-      hipLaunchKernelGGL(knn_cell_centre_kernel, dim3((unsigned)ncells), dim3(256), 0, st, (const double*)b.cpart, d, (const int64_t*)b.cell_starts, n, ncells,
-                         b.cen);
-      hipLaunchKernelGGL(knn_cell_rad_kernel, dim3((unsigned)ncells, CELL_SPLIT), dim3(256), (size_t)(d + 256) * 8, st, (const double*)b.X, d,
-                         (const int64_t*)b.cell_starts, n, ncells, (const double*)b.cen, prad);
-      hipLaunchKernelGGL(knn_cell_radfin_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, (const double*)prad,
-                         (const int64_t*)b.cell_starts, n, ncells, b.rad);
-      hipLaunchKernelGGL(knn_runs_kernel, dim3((unsigned)((nqb + 255) / 256)), dim3(256), 0, st, (const unsigned char*)nullptr,
-                         (const int64_t*)b.cell_starts, n, ncells, BR, q0, q1, nqb, b.maxruns, b.runs, b.nruns, (unsigned long long*)nullptr);
-      GLX_HIP(hipGetLastError());
-      GLX_POOL(glx_pool_alloc((void**)&b.pre_d, (size_t)nq * 2 * KP * 4));
-      GLX_POOL(glx_pool_alloc((void**)&b.pre_i, (size_t)nq * 2 * KP * 4));
-      rc = knn_launch_tile_bf16(KP, NKB, b, n, q0, q1, seed_sub, st, cat, true);
-      if (rc) return rc;
-      rc = knn_launch_seed(KP, b, nq, q0, k, cerr, st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(knn_cellmask_kernel, dim3((unsigned)nqb), dim3(256), (size_t)16 * d * 8, st, (const double*)b.X, d, q0, q1, (const double*)b.cen,
-                         (const double*)b.rad, ncells, (const double*)b.ub2, b.mask);
-      GLX_POOL(glx_pool_alloc((void**)&b.visited, 8));
-      GLX_HIP(hipMemsetAsync(b.visited, 0, 8, st));
-      hipLaunchKernelGGL(knn_runs_kernel, dim3((unsigned)((nqb + 255) / 256)), dim3(256), 0, st, (const unsigned char*)b.mask,
-                         (const int64_t*)b.cell_starts, n, ncells, BR, q0, q1, nqb, b.maxruns, b.runs, b.nruns, b.visited);
-      GLX_HIP(hipGetLastError());
-      g_knn_stats[12] = (double)ncells;
-    }
-  } else {
-    GLX_POOL(glx_pool_alloc((void**)&b.Rf, (size_t)n * dpa * 4));
-    GLX_POOL(glx_pool_alloc((void**)&b.Qf, (size_t)n * dpa * 4));
-    hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean,
-                       n, d, dpa, b.Rf, b.Qf, b.qnorm);
-    GLX_HIP(hipGetLastError());
-  }
-  auto launch_tile = [&](int64_t c0, int64_t c1) {
-    return use_bf16 ? knn_launch_tile_bf16(KP, NKB, b, n, c0, c1, nsplit, st, cat, false) : knn_launch_tile_f32(KP, DH, nkb, b, n, c0, c1, nsplit, st);
-  };
-  if (!wide) {
-    rc = launch_tile(q0, q1);
-    if (rc) return rc;
-    GLX_HIP(hipEventRecord(b.e1, st));
-    rc = knn_launch_rerank(b, n, d, k, q0, nq, lists, KP, M, cerr, st);
-    if (rc) return rc;
-    GLX_HIP(hipEventRecord(b.e2, st));
-  } else {
-    // chunk by chunk: filter, re-rank (flags, dk2 and the flagged rows are numbered within the pass, the lists go to their final rows).
-    // Every chunk's stage boundaries have events of their own, read once the stream has drained: the host never waits between chunks.
-    hipEvent_t start = b.e0;
-    for (int64_t c0 = q0; c0 < q1; c0 += chunk) {
-      const int64_t c1 = std::min(q1, c0 + chunk);
-      if (c0 > q0) GLX_HIP(hipMemsetD32Async((hipDeviceptr_t)b.gtau, 0x7f800000, (size_t)(c1 - c0), st));   // (the filter's thresholds are per chunk row)
-      rc = launch_tile(c0, c1);
-      if (rc) return rc;
-      hipEvent_t et = b.e1, er = b.e2;                 // (the last chunk ends on the pass's own events: the fallback is timed from e2)
-      if (c1 < q1) {
-        GLX_HIP(hipEventCreate(&et));
-        chunk_ev.ev.push_back(et);
-        GLX_HIP(hipEventCreate(&er));
-        chunk_ev.ev.push_back(er);
-      }
-      GLX_HIP(hipEventRecord(et, st));
-      rc = knn_launch_rerank_wide(b, n, d, k, q0, c0, c1 - c0, lists, KP, M, cerr, st);
-      if (rc) return rc;
-      GLX_HIP(hipEventRecord(er, st));
-      chunk_marks.push_back({start, et, er});
-      start = er;
-    }
-  }
-  float h_rmax[2] = {0.f, 0.f};
-  int h_nbad = 0;
-  GLX_HIP(hipMemcpyAsync(&h_nbad, b.nbad, 4, hipMemcpyDeviceToHost, st));
-  GLX_HIP(hipMemcpyAsync(h_rmax, b.rmax, 8, hipMemcpyDeviceToHost, st));
-  unsigned long long h_visited = 0;
-  if (b.visited) GLX_HIP(hipMemcpyAsync(&h_visited, b.visited, 8, hipMemcpyDeviceToHost, st));
-  GLX_HIP(hipStreamSynchronize(st));
-  if (b.visited) {
-    g_knn_stats[11] = (double)h_visited / ((double)nqb * (double)ntiles);
-    if (timing) fprintf(stderr, "[glx] knn: cell pruning, %d cells: %.1f %% of the (query block, ref tile) pairs visited\n", ncells, 100.0 * g_knn_stats[11]);
-  }
-  stamp("tile + re-rank done, flags on the host");
-  GLX_CHECK(h_rmax[1] == 1.0f, GLX_EINVAL, "glx_knn_bruteforce: non-finite input");   // (the first host look at the centring pass)
-  struct { size_t n; size_t size() const { return n; } bool empty() const { return n == 0; } } rows = {(size_t)h_nbad};   // (the list itself is on the device: b.rows)
-  if (short_lists && KP < 64 && rows.size() > 64) {
-    // repair row by row, or search again with the long lists?  A fallback row streams the data once (measured: ~5 TB/s);
-    // the repeat costs about four tile-kernel times (fp32-input filter, longer lists)
-    // The first pass is priced by a MODEL, not by its measured time: the choice must not depend on who else uses the GPU (with six
-    // processes sharing it the measured pass came out long enough, once in thirty runs, to send 21 000 rows of
-    // tests/test_gpu_knn.py::test_search_on_data_sorted_by_locality through the row-by-row repair -- the right answer, the slow way).
-    // 1.26e10 (query, ref, 16-feature block) triples per ms: config 2's 0.78 ms for 70 000^2 pairs of two blocks.
-    const double share = b.visited ? std::max(g_knn_stats[11], 0.01) : 1.0;
-    // (the fp32-input filter runs at a quarter of that: profiles/r02_knn_filter_probe.txt, d = 64 / 128; 0.03 ms: launches + the host look of a tiny pass)
-    const double ms_first = std::max(0.03, (double)nq * (double)n * share * ((double)dpa / 16.0) / 1.26e10 * (use_bf16 ? 1.0 : 4.0));
-    // (one pass per row: knn_fallback_collect_kernel; wide: plus the ranking of about k refs per row, 12 ns each -- measured at
-    // config 2, k = 1024: 1332 rows in 19.4 ms)
-    const double ms_rows = (double)rows.size() * ((double)n * d * 8.0 / 5e9 + (wide ? 1.2e-5 * k : 0.0));
-    // (the wide plan's repeat -- the fp32-input filter with lists of 64 over as many ranges, and the re-rank of up to 4096
-    // candidates -- measured 52 and 83 times the model's first pass at config 2, k = 512 and 1024: priced at 60)
-    if (ms_rows > (wide ? 60.0 : 4.0) * ms_first) {
-      g_knn_stats[2] = (double)rows.size();
-      return KNN_ESCALATE;
-    }
-  }
-  if (!rows.empty() && wide) {
-    // the one-pass buffer from k (a power of two >= 2 k), sorted in LDS; rows in batches whose k-round buffers stay within 256 MiB
-    const size_t nr = rows.size();
-    int cap = FB_CAP;
-    while (cap < 2 * k) cap *= 2;
-    const size_t per_row = (size_t)FB_SPLIT * k * 12 + (size_t)cap * 12 + 8;
-    const size_t batch = std::max<size_t>(1, std::min(nr, ((size_t)256 << 20) / per_row));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_pd, batch * FB_SPLIT * k * 8));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_pi, batch * FB_SPLIT * k * 4));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_cnt, batch * 2 * 4));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_bd, batch * cap * 8));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_bi, batch * cap * 4));
-    for (size_t r0 = 0; r0 < nr; r0 += batch) {
-      rc = knn_launch_fallback_wide(b, n, d, k, q0, b.rows + r0, std::min(batch, nr - r0), cap, st);
-      if (rc) return rc;
-    }
-  } else if (!rows.empty()) {
-    const size_t nr = rows.size();
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_pd, nr * FB_SPLIT * k * 8));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_pi, nr * FB_SPLIT * k * 4));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_cnt, nr * 2 * 4));            // [nr] counts, [nr] redo marks
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_bd, nr * FB_CAP * 8));
-    GLX_POOL(glx_pool_alloc((void**)&b.fb_bi, nr * FB_CAP * 4));
-    GLX_HIP(hipMemsetAsync(b.fb_cnt, 0, nr * 2 * 4, st));
-    const int* fb_runs = (const int*)(b.visited ? b.runs : nullptr);   // (b.runs: the main pass's runs when the search was cell-pruned -- the pre-pass's were overwritten by them)
-    rc = knn_launch_fallback(b, n, d, k, q0, nr, fb_runs, BR, st);
-    if (rc) return rc;
-  }
-  GLX_HIP(hipEventRecord(b.e3, st));
-  if (ind_out) GLX_UP(glx_download(ind_out, b.ind, (size_t)nq * k * 8, st, __func__));
-  if (dist_out) GLX_UP(glx_download(dist_out, b.dist, (size_t)nq * k * 8, st, __func__));
-  GLX_HIP(hipStreamSynchronize(st));
-  stamp("results on the host");
-  if (perm_pending) {    // the permutation stays on the device with the result (glx_knn_result_order copies it into the caller's --
-    glx_pool_free(capture->order_dev);      // page-locked -- array: a synchronous copy into fresh pageable memory cost 8 ms here)
-    capture->order_dev = b.orig;
-    b.orig = nullptr;
-  }
-  if (capture) {         // the lists stay on the device with the caller's result object (everything that writes them has finished)
-    glx_pool_free(capture->ind);
-    glx_pool_free(capture->dist);
-    capture->ind = b.ind;
-    capture->dist = b.dist;
-    capture->n = n;
-    capture->k = k;
-    capture->device = device;
-    b.ind = nullptr;
-    b.dist = nullptr;
-  }
-  float ms_tile = 0, ms_rr = 0, ms_fb = 0;
-  GLX_HIP(hipEventElapsedTime(&ms_tile, b.e0, b.e1));
-  GLX_HIP(hipEventElapsedTime(&ms_rr, b.e1, b.e2));
-  GLX_HIP(hipEventElapsedTime(&ms_fb, b.e2, b.e3));
-  if (wide) {                // (the sum over the chunks; a later chunk's filter time includes the reset of the thresholds)
-    ms_tile = ms_rr = 0;
-    for (const auto& m : chunk_marks) {
-      float t = 0, r = 0;
-      GLX_HIP(hipEventElapsedTime(&t, m[0], m[1]));
-      GLX_HIP(hipEventElapsedTime(&r, m[1], m[2]));
-      ms_tile += t;
-      ms_rr += r;
-    }
-  }
-  g_knn_stats[0] = ms_tile;
-  g_knn_stats[1] = ms_rr;
-  g_knn_stats[2] = (double)rows.size();
-  g_knn_stats[3] = ms_tile + ms_rr + ms_fb;
-  g_knn_stats[4] = ms_fb;
-  g_knn_stats[5] = (double)dpa;
-  g_knn_stats[6] = (double)nsplit;
-  g_knn_stats[7] = use_bf16 ? -(double)KP : (double)KP;   // negative: the bf16 filter ran
-  g_knn_stats[13] = (double)nchunks;
-  g_knn_stats[14] = wide ? 1.0 : 0.0;
-  g_knn_stats[15] = (double)ncand;
-  return GLX_OK;
+  KnnPass s = {X, n, d, k, q0, q1, nq, ind_out, dist_out, device, long_lists, capture, cell_starts, ncells,
+               knn_make_plan(n, d, k, nq, long_lists, g_knn_opt), stamp};
+  GLX_UP(s.upload_features());
+  GLX_UP(s.form_cells(auto_cells));
+  GLX_UP(s.centre_and_alloc_lists());
+  GLX_UP(s.prepare_operands());
+  GLX_UP(s.filter_and_rerank());
+  GLX_UP(s.host_look());             // (KNN_ESCALATE included)
+  GLX_UP(s.fallback());
+  return s.finish();
 }
 
 static int knn_run(const double* X, int64_t n, int d, int k, int64_t q0, int64_t q1, int64_t* ind_out, double* dist_out, int device,
                    glx_knn_result* capture = nullptr, const int64_t* cell_starts = nullptr, int ncells = 0, int auto_cells = 0) {
-  g_knn_stats[8] = 0.0;
-  g_knn_stats[10] = g_knn_stats[11] = g_knn_stats[12] = 0.0;
+  g_knn_stats[KS_ESCALATED_ROWS] = 0.0;
+  g_knn_stats[KS_SEED_SAMPLE] = g_knn_stats[KS_VISITED_SHARE] = g_knn_stats[KS_CELLS] = 0.0;
   int rc = knn_pass(X, n, d, k, q0, q1, ind_out, dist_out, device, false, capture, cell_starts, ncells, auto_cells);
   if (rc != KNN_ESCALATE) return rc;
-  const double flagged = g_knn_stats[2];
-  g_knn_stats[10] = g_knn_stats[11] = g_knn_stats[12] = 0.0;
+  const double flagged = g_knn_stats[KS_FALLBACK_ROWS];
+  g_knn_stats[KS_SEED_SAMPLE] = g_knn_stats[KS_VISITED_SHARE] = g_knn_stats[KS_CELLS] = 0.0;
   if (capture) { capture->order.clear(); glx_pool_free(capture->order_dev); capture->order_dev = nullptr; }
   rc = knn_pass(X, n, d, k, q0, q1, ind_out, dist_out, device, true, capture);     // (long lists: the fp32-input kernel, all refs)
-  g_knn_stats[8] = flagged;            // rows the first (short-list) pass could not accept
+  g_knn_stats[KS_ESCALATED_ROWS] = flagged;            // rows the first (short-list) pass could not accept
   return rc;
 }
 

@@ -1,6 +1,8 @@
 // Shared by the translation units of the exact kNN search (weightmatrix.knnsearch of the reference,
 // graphlearning/weightmatrix.py:297-429):
 //   knn.hip            the driver (one pass of the search, the escalation, the C-ABI entry points)
+//   knn_plan.h         the plan of a pass (list length, tile width, ref ranges, candidates, chunks ...) and the constants it shares
+//                      with the tile kernels; no HIP header, checked on the host (tests/test_knn_plan.py)
 //   knn_prep.hip       centring, the filter's operand images, the seeding pre-pass's thresholds
 //   knn_tile_bf16_*.hip / knn_tile_f32_*.hip   the MFMA candidate filters (knn_tile_bf16.h / knn_tile_f32.h hold the kernels;
 //                      one translation unit per list length so that they compile side by side)
@@ -8,7 +10,9 @@
 //   knn_rerank.hip     the exact fp64 re-rank with its acceptance test, the exact fallback
 #pragma once
 #include "glx_internal.h"
+#include "knn_plan.h"
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 
@@ -17,44 +21,21 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-static const int BQ = 128;             // queries per workgroup (4 waves x 32)
-static const int BR_MAX = 128;         // refs per LDS tile: 32 * NSUB
-static const int KBUF = 8;             // per-lane append slots between list merges
 static const int KNN_PAD_ROWS = 256;   // spare rows behind Xb / nrm (>= the widest ref tile): the staging loads of the last tile need no predicates
-static const int KNN_CAT_SEG = 21;     // concatenated split operands: three segments of this many bf16 per row (d <= 21)
 static const int CENTRE_ROWS = 512;    // rows per workgroup of the column-sum pass
 static const int CELL_SPLIT = 64;      // workgroups per cell in the centre / radius passes (a cell of config 4 at n = 1e7 is 80 MB)
-static const int FB_SPLIT = 64;        // pieces a fallback row's refs are cut into
 static const int FB_CACHE = 2048;      // a piece of at most this many refs keeps its distances in LDS between the rounds
-static const int FB_CAP = 128;         // candidates per row the one-pass fallback can hold
-static const int KNN_K_NARROW = 60;    // neighbours (self included) of the list-returning entry points and of the register re-rank
-static const int KNN_K_MAX = 1024;     // neighbours (self included) of the wide search (glx_knn_search)
-static const size_t KNN_CAND_BUDGET = (size_t)1 << 30;   // bytes of candidates (value + index) a wide pass holds at once: its query chunks
 
-// features per half per block of the blocked (d > 130) fp32 variant; 16 where the KP = 64 lists leave less LDS
-constexpr int knn_kb(int KP) { return KP == 64 ? 16 : 32; }   // (KP = 8 never takes the blocked variant)
+// the slots of glx_knn_stats (include/glx_experimental.h describes them)
+enum KnnStat {
+  KS_TILE_MS, KS_RERANK_MS, KS_FALLBACK_ROWS, KS_TOTAL_MS, KS_FALLBACK_MS, KS_DPA, KS_NSPLIT, KS_KP /* negative: the bf16 filter ran */,
+  KS_ESCALATED_ROWS, KS_CONCAT, KS_SEED_SAMPLE, KS_VISITED_SHARE, KS_CELLS, KS_CHUNKS, KS_WIDE, KS_CANDIDATES, KS_COUNT
+};
+static_assert(KS_COUNT == 16, "glx_knn_stats hands out 16 doubles");
 
-// fp32-input filter: refs per tile = 32*NSUB, as many as fit LDS (160 KiB) beside the candidate lists
-constexpr int tile_nsub(int DH, int KP) {
-  const int stride = 2 * DH + 2;
-  if (KP == 8) {   // short lists: aim at three workgroups per CU
-    for (int ns = 4; ns >= 2; ns /= 2)
-      if (2 * 32 * ns * stride * 4 + (KP + KBUF) * 256 * 8 <= 53 * 1024) return ns;
-    return 1;
-  }
-  for (int ns = 4; ns >= 2; ns /= 2)
-    if (2 * 32 * ns * stride * 4 + (KP + KBUF) * 256 * 8 <= 78 * 1024) return ns;   // two workgroups per CU
-  return 1;
-}
-
-// bf16 filter: refs per tile = 32 * NSUB.  Measured (one box): 16-32 features: NSUB 2 (config 2: 1.88 vs 2.12 ms, config 3: 2.74 vs
-// 3.09 ms); 64 features: NSUB 1 -- a 17 KB tile lets three workgroups share a CU (n = 1e6: 376 vs 401 ms)
-constexpr int bf16_nsub(int NKB, int KP) { return (NKB >= 4 || KP >= 32) ? 1 : 2; }
-// 8-entry lists in registers where that buys a fourth workgroup per CU (d = 49 .. 64: 122 registers, 34 KB of LDS; measured
-// +4 % at n = 3e5 .. 1e6; at fewer feature blocks the registers spill, at more the kernel is register-bound anyway)
-constexpr bool bf16_reglists(int NKB, int KP) { return KP == 8 && NKB == 4; }
-
-// device buffers of one pass of the search (pooled blocks; the destructor drains the stream first)
+// What one pass of the search works on: the pooled device blocks, the host arrays its asynchronous uploads read, the work set
+// (stream + events) and the events of the wide plan's chunks.  The destructor drains the stream(s) before anything is handed back,
+// and the host arrays are members, destroyed after it: nothing the stream may still read goes away under it, wherever a pass returns.
 struct KnnBufs {
   unsigned short* Xb = nullptr;      // bf16 hi | lo image (bf16 filter); concatenated form: the ref image [hi | hi | lo]
   unsigned short* Xq = nullptr;      // concatenated form only: the query image [hi | lo | hi]
@@ -83,9 +64,21 @@ struct KnnBufs {
   glx_work* work = nullptr;           // the device's cached stream + events
   hipStream_t stream = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+  // cells formed by the library, host side: the sample rows, every row's cell, the rows by cell, the cells' places in the chain,
+  // the centres, the cells' first rows
+  std::vector<int> oc_sample, oc_cid, oc_perm, oc_place;
+  std::vector<double> oc_cen;
+  std::vector<int64_t> own_starts;
+  // the wide plan: the events created for the chunks before the last, and per chunk its start, filter done, re-rank done
+  std::vector<hipEvent_t> chunk_ev;
+  std::vector<std::array<hipEvent_t, 3>> chunk_marks;
+  KnnBufs() = default;
+  KnnBufs(const KnnBufs&) = delete;
+  KnnBufs& operator=(const KnnBufs&) = delete;
   ~KnnBufs() {
     if (stream) hipStreamSynchronize(stream);   // pooled blocks are reused at once: nothing may still be running on them
     if (work && work->side) hipStreamSynchronize(work->side);
+    for (hipEvent_t e : chunk_ev) hipEventDestroy(e);
     void* blocks[] = {Xb, Xq, nrm, part, rmax, X, mean, dist, Rf, Qf, qnorm, cand_d, pre_d, pre_i, runs, nruns, cell_starts, cen, rad, ub2, cpart,
                       mask, visited, Xraw, orig, cell_id, cand_i, flags, rows, fb_pi, gtau, fb_pd, dk2, fb_bd, fb_cnt, fb_bi, nbad, place, bh, ind};
     for (void* p : blocks) glx_pool_free(p);

@@ -1,0 +1,162 @@
+"""graphlearning_amd/csrc/knn_plan.h, the plan of one pass of the exact kNN search (list length, tile width, ref ranges, candidate
+count, query chunks, the filter's error constant, the seeding / escalation / wide-fallback decisions) and the chain of the cells:
+built on the host with no HIP header (tests/knn_plan_host.cpp) and compared with the table recorded from the search pass as it
+stood before the plan was a header of its own (tests/golden/knn_plans.txt)."""
+import hashlib
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'knn_plans.txt')
+BQ = 128
+KNN_CAND_BUDGET = 1 << 30
+FIELDS = ('KP', 'DH', 'nkb', 'NKB', 'dpa', 'BR', 'ntiles', 'nsplit', 'lists', 'ncand', 'M', 'chunk', 'nchunks', 'short_lists', 'wide',
+          'use_bf16', 'cat')
+
+
+@pytest.fixture(scope='module')
+def driver():
+    exe = os.path.join(tempfile.mkdtemp(), 'knn_plan_host')
+    subprocess.run(['g++', '-std=c++17', '-O1', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'graphlearning_amd', 'csrc'), '-o', exe,
+                    os.path.join(ROOT, 'tests', 'knn_plan_host.cpp')], check=True)
+
+    def run(*args):
+        r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (args, r.returncode, r.stderr[-4000:])
+        return r.stdout
+    return run
+
+
+@pytest.fixture(scope='module')
+def golden():
+    digests, rows, extras = {}, [], []
+    for line in open(GOLDEN).read().split('\n'):
+        if not line or line.startswith('#'):
+            continue
+        if line.startswith('sha256 '):
+            digests[line.split()[1]] = line.split()[2]
+        elif line[0] in 'SEF':
+            extras.append(line)
+        else:
+            rows.append(line)
+    return digests, rows, extras
+
+
+def parse(row):
+    """(n, d, k, nq, long_lists, overrides, concat), {field: value}"""
+    case, plan = row.split(' | ')
+    vals = plan.split()
+    p = {f: int(v) for f, v in zip(FIELDS, vals)}
+    p['cerr'] = vals[len(FIELDS)]
+    return tuple(int(v) for v in case.split()), p
+
+
+@pytest.fixture(scope='module')
+def plans(driver):
+    out = driver('plans')
+    return out, dict(parse(r) for r in out.split('\n') if r)
+
+
+def test_every_plan_of_the_grid_is_the_recorded_one(plans, golden):
+    out, _ = plans
+    digests, rows, _ = golden
+    got = set(out.split('\n'))
+    missing = [r for r in rows if r not in got]      # (the readable rows first: they say WHICH plan moved)
+    assert not missing, 'plans that differ from the recorded ones (recorded rows shown):\n' + '\n'.join(missing[:20])
+    assert out.count('\n') == 11662
+    assert hashlib.sha256(out.encode()).hexdigest() == digests['plans']
+
+
+def test_seeding_escalation_and_wide_fallback_decisions_are_the_recorded_ones(driver, golden):
+    digests, _, extras = golden
+    out = driver('extras')
+    got = [r for r in out.split('\n') if r]
+    assert len(got) == len(extras)
+    diff = [(g, w) for g, w in zip(got, extras) if g != w]
+    assert not diff, 'decisions that differ (got, recorded):\n' + '\n'.join('%s\n%s' % gw for gw in diff[:20])
+    assert hashlib.sha256(out.encode()).hexdigest() == digests['extras']
+    # the thresholds the grid is there to cross
+    rows = {r.split(' | ')[0]: r.split(' | ')[1] for r in got}
+    assert rows['F 61 1'].split()[0] == '128' and rows['F 64 1'].split()[0] == '128'
+    assert rows['F 65 1'].split()[0] == '256' and rows['F 1024 1'].split()[0] == '2048'
+    assert any(r.startswith('E ') and ' 64:0 65:1 ' in r for r in got)                      # more than 64 flagged rows
+    assert rows['S 70000 20 60 70000 0 16'] == '8 1' and rows['S 70000 20 61 70000 0 16'] == '8 0'    # never the wide plan
+    assert rows['S 70000 20 12 70000 0 1'] == '0 0' and rows['S 70000 20 12 70000 0 -1'] == '0 0'   # one cell, no cells
+
+
+def test_anchor_plans(plans):
+    _, p = plans
+    default = (0, -1)
+
+    def plan(n, d, k, nq, long_lists):
+        return p[(n, d, k, nq, int(long_lists)) + default]
+
+    def has(q, **want):
+        got = {f: q[f] for f in want}
+        assert got == want, (got, want)
+    # config 2 of the benchmark: the split-bf16 filter with 8 lists of 8; its long-list repeat on the fp32-input filter
+    has(plan(70000, 20, 12, 70000, False), use_bf16=1, KP=8, nsplit=4, ncand=64, cat=2, nchunks=1, cerr='0x1.3ap-15')
+    has(plan(70000, 20, 12, 70000, True), use_bf16=0, KP=16, BR=128, nsplit=2, cerr='0x1p-17')
+    # the wide plan
+    has(plan(70000, 20, 128, 70000, False), lists=16, KP=32, ncand=512)
+    has(plan(70000, 20, 1024, 70000, False), lists=64, KP=32, ncand=2048, chunk=65536, nchunks=2)
+    has(plan(70000, 20, 1024, 70000, True), lists=64, KP=64, ncand=4096, chunk=32768, nchunks=3)
+    for long_lists in (False, True):
+        has(plan(70000, 784, 1024, 70000, long_lists), use_bf16=0, DH=16, nkb=25, dpa=800)
+
+
+def test_invariants_of_every_plan(plans):
+    _, p = plans
+    assert len(p) == 11662
+    for (n, d, k, nq, long_lists, overrides, concat), q in p.items():
+        case = (n, d, k, nq, long_lists, overrides, concat, q)
+        assert q['lists'] == 2 * q['nsplit'], case
+        assert q['ncand'] == q['lists'] * q['KP'], case
+        M = 64
+        while M < q['ncand']:
+            M *= 2
+        assert q['M'] == M, case
+        if q['wide'] and q['chunk'] > BQ:
+            assert q['chunk'] * q['ncand'] * 8 <= KNN_CAND_BUDGET, case
+        if q['use_bf16']:
+            assert q['short_lists'] and d <= 128 and q['KP'] <= 32, case
+        if q['wide']:
+            assert q['ncand'] >= k, case
+
+
+def chain_places(cen):
+    """The greedy chain of nearest centres from the centre farthest from the centres' mean, on every cfs-th feature; sums in the
+    header's order (feature by feature, left to right)."""
+    m, d = cen.shape
+    mean = np.zeros(d)
+    for c in range(m):
+        mean += cen[c] / m
+    sub = np.arange(0, d, (d + 31) // 32)
+
+    def dist2(a, b):
+        t = np.zeros(len(a))
+        for f in sub:
+            t += (a[:, f] - b[f]) ** 2
+        return t
+    cur = int(np.argmax(dist2(cen, mean)))
+    place = np.full(m, -1)
+    for pos in range(m):
+        place[cur] = pos
+        t = np.where(place < 0, dist2(cen, cen[cur]), np.inf)
+        cur = int(np.argmin(t))
+    return place
+
+
+@pytest.mark.parametrize('m,d', [(1, 3), (2, 20), (37, 3), (128, 20), (512, 64), (300, 100)])
+def test_chain_of_the_cells(driver, m, d):
+    rng = np.random.default_rng(1000 * m + d)
+    cen = rng.standard_normal((m, d)) * rng.uniform(0.1, 10.0, size=d)
+    path = os.path.join(tempfile.mkdtemp(), 'cen.bin')
+    cen.tofile(path)
+    got = np.array(driver('chain', path, m, d).split(), dtype=np.int64)
+    assert np.array_equal(np.sort(got), np.arange(m))
+    assert np.array_equal(got, chain_places(cen))
