@@ -1,18 +1,20 @@
 """Mirrors reference examples/plaplace.py: p-Laplace interpolation of boundary values on a random
-geometric graph.  (The reference example builds an epsilon-ball graph, which is outside this package;
-a kNN graph of the same points is used instead.)  fast=False selects the Jacobi iteration of the
-reference's C extension, which runs on the GPU; the reference's default fast=True is a sequential
-Gauss-Seidel sweep and is not provided."""
+geometric graph, the epsilon-ball graph of the reference example (weightmatrix.epsilon_ball, built on
+the GPU).  fast=False selects the Jacobi iteration of the reference's C extension, which runs on the
+GPU; the reference's default fast=True is a sequential Gauss-Seidel sweep and is not provided."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import graphlearning_amd as gl
 
-X = np.random.default_rng(0).random((int(1e4), 2))
+X = np.random.default_rng(2).random((int(1e4), 2))      # (a seed whose graph has no isolated vertex: minimum degree 2)
 x, y = X[:, 0], X[:, 1]
-W = gl.weightmatrix.knn(X, 12)
-G = gl.graph(W)
 eps = 0.02
+t0 = time.perf_counter()
+W = gl.weightmatrix.epsilon_ball(X, eps)
+print('epsilon-ball graph (eps=%g) of %d points: %d entries, degrees %d..%d, in %.1f ms'
+      % (eps, len(x), W.nnz, np.diff(W.indptr).min(), np.diff(W.indptr).max(), 1e3 * (time.perf_counter() - t0)))
+G = gl.graph(W)
 bdy_set = (x < eps) | (x > 1 - eps) | (y < eps) | (y > 1 - eps)
 bdy_val = (x - 0.5) ** 2 + (y - 0.5) ** 2
 t0 = time.perf_counter()

@@ -148,6 +148,11 @@ _SIGNATURES = {
     'glx_knn_result_order': [_vp, _vp],
     'glx_knn_result_to_csr': [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, C.POINTER(C.c_int64)],
     'glx_knn_result_destroy': [_vp],
+    'glx_ball_search': [_vp, C.c_int64, C.c_int, C.c_double, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
+    'glx_ball_result_nnz': [_vp, _i64p],
+    'glx_ball_result_to_csr': [_vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _i64p],
+    'glx_ball_result_destroy': [_vp],
+    'glx_ball_stats': [_f64p],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1254,6 +1259,80 @@ class KnnResult:
             self.close()
         except Exception:
             pass
+
+
+class BallResult:
+    """A finished radius search whose structure lives on the device (glx_ball_search): `to_csr` weighs it and returns the
+    scipy CSR matrix, `structure()` returns it with the distances the weights see instead (for kernels evaluated on the host)."""
+
+    def __init__(self, X, epsilon, features=None, device=None):
+        X = _dense(X, np.float64, name='data')
+        n, d = X.shape
+        F = None if features is None else _dense(features, np.float64, name='features')
+        if F is not None and (F.ndim != 2 or F.shape[0] != n):
+            raise GlxError('features have shape %s, expected (%d, m)' % (F.shape, n))
+        self.n, self.device, self.has_features = n, _dev(device), F is not None
+        self._h = _vp()
+        check(load().glx_ball_search(_ptr(X), n, d, float(epsilon), _ptr(F), 0 if F is None else F.shape[1], self.device,
+                                     C.byref(self._h)), 'glx_ball_search')
+        nnz = C.c_int64(0)
+        check(load().glx_ball_result_nnz(self._h, C.byref(nnz)), 'glx_ball_result_nnz')
+        self.nnz = nnz.value
+
+    def _arrays(self, specs):
+        pinned = sum(int(np.prod(shape)) * np.dtype(dt).itemsize for shape, dt in specs) <= _PINNED_CSR_MAX
+        return [(pinned_empty(shape, dt) if pinned else np.empty(shape, dt)) for shape, dt in specs]
+
+    def _csr(self, indptr, col, val, m):
+        from scipy import sparse
+        if 2 * m < self.nnz:        # zero weights were dropped: a view would keep the full-size (page-locked) block alive behind it
+            val, col = val[:m].copy(), col[:m].copy()
+        W = sparse.csr_matrix((val[:m], col[:m], indptr), shape=(self.n, self.n))
+        W.has_sorted_indices = True
+        W.has_canonical_format = True
+        return W
+
+    def to_csr(self, kernel='gaussian', epsilon_f=1.0):
+        """The weight matrix of one of the device kernels ('uniform', 'gaussian', 'distance', 'singular'), zero weights dropped."""
+        indptr, col, val = self._arrays([((self.n + 1,), np.int32), ((self.nnz,), np.int32), ((self.nnz,), np.float64)])
+        m = C.c_int64(0)
+        check(load().glx_ball_result_to_csr(self._h, _KERNEL_ID[kernel], float(epsilon_f), _ptr(indptr), _ptr(col), _ptr(val), None, None,
+                                            C.byref(m)), 'glx_ball_result_to_csr')
+        return self._csr(indptr, col, val, m.value)
+
+    def structure(self):
+        """(indptr, indices, dists, fdists): the rows (ascending columns, nothing dropped) and, entry by entry, the squared
+        distance in numpy's summation order and the squared feature distance (None without features)."""
+        specs = [((self.n + 1,), np.int32), ((self.nnz,), np.int32), ((self.nnz,), np.float64)]
+        if self.has_features:
+            specs.append(((self.nnz,), np.float64))
+        arrs = self._arrays(specs)
+        indptr, col, dists = arrs[:3]
+        fd = arrs[3] if self.has_features else None
+        m = C.c_int64(0)
+        check(load().glx_ball_result_to_csr(self._h, _KERNEL_ID['given'], 1.0, _ptr(indptr), _ptr(col), None, _ptr(dists), _ptr(fd),
+                                            C.byref(m)), 'glx_ball_result_to_csr')
+        return indptr, col[:m.value], dists[:m.value], (None if fd is None else fd[:m.value])
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            lib = load(required=False)
+            if lib is not None:
+                lib.glx_ball_result_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ball_stats():
+    out = (C.c_double * 8)()
+    check(load().glx_ball_stats(out), 'glx_ball_stats')
+    return dict(pairs_tested=out[0], pairs_accepted=out[1], cells=int(out[2]), grid_ms=out[3], count_ms=out[4], fill_ms=out[5],
+                sort_ms=out[6], weights_ms=out[7])
 
 
 def exp_cr(x, device=None):

@@ -2,28 +2,9 @@
 // fallback for the rows that fail it (see knn.hip; reference graphlearning/weightmatrix.py:349-352, whose cKDTree answer this
 // reproduces bit for bit).
 #include "knn_internal.h"
+#include "sqdist_tree.h"   // sqdist_exact: the tree's accumulation order (shared with ball.hip)
 
 // ---- stage 2: exact fp64 re-rank + acceptance check ------------------------------------------
-// squared distance with the accumulation pattern of scipy's ckdtree sqeuclidean_distance_double
-// (4 partial sums over blocks of 4 coordinates, combined left to right, then the tail)
-__device__ __forceinline__ double sqdist_exact(const double* __restrict__ u, const double* __restrict__ v, int d) {
-#pragma clang fp contract(off)
-  double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
-  int i = 0;
-  for (; i + 4 <= d; i += 4) {
-    const double d0 = u[i] - v[i], d1 = u[i + 1] - v[i + 1], d2 = u[i + 2] - v[i + 2], d3 = u[i + 3] - v[i + 3];
-    a0 = a0 + d0 * d0;
-    a1 = a1 + d1 * d1;
-    a2 = a2 + d2 * d2;
-    a3 = a3 + d3 * d3;
-  }
-  double s = a0 + a1 + a2 + a3;
-  for (; i < d; ++i) {
-    const double dd = u[i] - v[i];
-    s = s + dd * dd;
-  }
-  return s;
-}
 
 __device__ __forceinline__ bool lex_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
 

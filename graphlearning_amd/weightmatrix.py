@@ -94,6 +94,74 @@ def knn(data, k, kernel='gaussian', eta=None, symmetrize=True, metric='raw', sim
     return W
 
 
+def epsilon_ball(data, epsilon, kernel='gaussian', features=None, epsilon_f=1, eta=None, device=None):
+    """Epsilon-ball weight matrix, same signature and result as reference weightmatrix.py:189-294 (plus `device`): a scipy CSR
+    (n,n) float64 matrix with w_ij = eta(|x_i - x_j|^2 / epsilon^2) where |x_i - x_j| <= epsilon, symmetric bit for bit, empty
+    diagonal, canonical format; with `features` (n,m) every weight is multiplied by the same kernel of the feature distance
+    with `epsilon_f`.  kernel: 'uniform', 'gaussian', 'distance', 'singular'; `eta` (a callable) overrides it.
+
+    Searched, weighted and assembled on the device.  Membership is the rule of the reference's cKDTree.query_pairs: the
+    squared distance in the tree's own accumulation order <= epsilon*epsilon (a pair AT distance epsilon belongs); the weights
+    see numpy's row sum of the squared differences, as in the reference.  Entries whose weight is exactly zero are dropped.
+    The Gaussian exponential follows `knn`: correctly rounded on the device, numpy's on the host under GLX_HOST_EXP=1; `eta`
+    is evaluated on the host over the distances the device hands back.  A negative or NaN epsilon and non-finite data are
+    refused (the reference returns a meaningless graph for epsilon < 0)."""
+    # validate before anything is launched
+    if eta is None and kernel not in ['uniform', 'gaussian', 'distance', 'singular']:
+        sys.exit('Invalid choice of kernel: ' + kernel)
+    if not epsilon >= 0:
+        raise ValueError('epsilon_ball: epsilon must not be negative or NaN (got %r)' % (epsilon,))
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+        raise ValueError('epsilon_ball: data must be (n, m) with n, m >= 1 (got shape %s)' % (data.shape,))
+    if not np.isfinite(data).all():
+        raise ValueError('epsilon_ball: data must be finite')
+    if features is not None:
+        features = np.ascontiguousarray(features, dtype=np.float64)
+        if features.ndim != 2 or features.shape[0] != data.shape[0] or features.shape[1] < 1:
+            raise ValueError('epsilon_ball: features must be (n, k) with the rows of data (got shape %s)' % (features.shape,))
+        if not np.isfinite(features).all():
+            raise ValueError('epsilon_ball: features must be finite')
+    n = data.shape[0]
+    host_exp = os.environ.get('GLX_HOST_EXP') == '1' and eta is None and kernel == 'gaussian'
+    res = _hip.BallResult(data, epsilon, features=features, device=device)
+    try:
+        if res.nnz == 0:
+            return sparse.csr_matrix((n, n))         # no pair at all (reference :241-242)
+        if eta is None and not host_exp:
+            W = res.to_csr(kernel=kernel, epsilon_f=epsilon_f)
+        else:
+            indptr, indices, dists, fdists = res.structure()
+            with np.errstate(all='ignore'):
+                if eta is None:
+                    weights = np.exp(-4 * dists / (epsilon * epsilon))
+                    if fdists is not None:
+                        weights = weights * np.exp(-4 * fdists / (epsilon_f * epsilon_f))
+                else:
+                    weights = np.asarray(eta(dists / (epsilon * epsilon)), dtype=np.float64)
+                    if fdists is not None:
+                        weights = weights * eta(fdists / (epsilon_f * epsilon_f))
+            W = _drop_zeros(n, indptr, indices, weights)
+    finally:
+        res.close()
+    # each pair is decided and weighed by the same expression from both sides: symmetric bit for bit, empty diagonal
+    W._glx_sym = utils.symmetric_fingerprint(W)
+    return W
+
+
+def _drop_zeros(n, indptr, indices, weights):
+    """CSR (n,n) of the entries whose weight is not exactly zero (the reference's eliminate_zeros), order kept."""
+    keep = weights != 0
+    if not keep.all():
+        kept_before = np.concatenate(([0], np.cumsum(keep, dtype=np.int64)))
+        indptr = kept_before[indptr].astype(np.int32)
+        indices, weights = indices[keep], weights[keep]
+    W = sparse.csr_matrix((weights, indices, indptr), shape=(n, n))
+    W.has_sorted_indices = True
+    W.has_canonical_format = True
+    return W
+
+
 def _assemble(res, knn_ind, knn_dist, k, kernel, sym, weights, device):
     if res is not None:
         return res.to_csr(k, kernel=kernel, sym=sym, weights=weights)

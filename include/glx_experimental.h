@@ -151,6 +151,27 @@ int glx_cg_last_stop_margin(glx_graph* A, double* margin_out);
  * than 8192 rows, a 1-D right-hand side) or no solve yet. */
 int glx_cg_last_block_stats(glx_graph* A, int* out4);
 
+/* ---- exact radius graphs: weightmatrix.epsilon_ball (csrc/ball.hip) -------------------------------------------------------
+ * The unordered pair {i, j}, i != j, is an edge iff the squared distance in the accumulation order of scipy's cKDTree
+ * (csrc/sqdist_tree.h) is <= fl(epsilon * epsilon).  glx_ball_search finds the structure (X (n, d) and the optional features
+ * F (n, m_f) are host arrays, finite; epsilon >= 0) and keeps it on the device: rows of ascending columns, no diagonal.
+ * GLX_EUNSUPPORTED (with the count in the message) when the graph has more than 2^31 - 1 entries.  OWNERSHIP: the caller owns
+ * *out and releases it with glx_ball_result_destroy; the other calls borrow it.
+ * glx_ball_result_to_csr weighs the entries -- distances summed in numpy's order (csrc/npsum_exact.h), times the same kernel of
+ * the feature distance with epsilon_f when the search had features -- and drops those whose weight is exactly zero.  kernel:
+ * 1 uniform, 2 gaussian (correctly rounded exp), 4 distance, 5 singular, or 0: structure and distances only (val = 1, nothing
+ * dropped; the caller weighs on the host).  rowptr [n + 1]; col, val, dists_out, fdists_out [glx_ball_result_nnz] (val and
+ * either distance output may be NULL; distances only where nothing is dropped); *nnz_out = entries written.
+ * glx_ball_stats, of the calling thread's last search: [0] pairs tested, [1] pairs accepted (= entries), [2] cells, device ms of
+ * [3] the grid passes, [4] count + scan, [5] fill, [6] the row sorts, [7] weights + second scan of the last glx_ball_result_to_csr. */
+typedef struct glx_ball_result glx_ball_result;
+int glx_ball_search(const double* X, int64_t n, int d, double epsilon, const double* F, int m_f, int device, glx_ball_result** out);
+int glx_ball_result_nnz(const glx_ball_result* res, int64_t* nnz_out);
+int glx_ball_result_to_csr(const glx_ball_result* res, int kernel, double epsilon_f, int32_t* rowptr, int32_t* col, double* val,
+                           double* dists_out, double* fdists_out, int64_t* nnz_out);
+int glx_ball_result_destroy(glx_ball_result* res);
+int glx_ball_stats(double stats[8]);
+
 #ifdef __cplusplus
 }
 #endif
