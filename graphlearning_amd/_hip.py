@@ -153,6 +153,7 @@ _SIGNATURES = {
     'glx_ball_result_to_csr': [_vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _i64p],
     'glx_ball_result_destroy': [_vp],
     'glx_ball_stats': [_f64p],
+    'glx_sssp': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp, _i64p, _f64p, C.c_int],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1055,6 +1056,46 @@ def lp_iterate(uu, ul, nbr, row, W, ind, val, p, T, tol, device=None):
     check(load().glx_lp_iterate(_ptr(uu), _ptr(ul), _ptr(nbr), _ptr(row), _ptr(W), _ptr(ind), _ptr(val), float(p), int(T), float(tol),
                                 len(uu), len(W), len(ind), C.byref(it), _dev(device)), 'glx_lp_iterate')
     return it.value
+
+
+GLX_SSSP_PLAIN, GLX_SSSP_HOPF_LAX = 0, 1
+
+
+SSSP_FULL_SWEEPS = False        # True: every round looks at every value (no out-edge lists are handed over); same results, for measurement
+sssp_last_ms = None             # host milliseconds of the last call: uploads, distance rounds, closest-point rounds, downloads
+
+
+def sssp(in_ptr, in_idx, in_cost, src_ptr, src_idx, src_val, max_dist=np.inf, hopf_lax=False, return_cp=False, device=None,
+         out_ptr=None, out_idx=None):
+    """Shortest-path distances of B = len(src_ptr) - 1 problems on one graph given by its in-edge lists (glx_sssp, csrc/sssp.hip):
+    returns (dist (n, B) float64, cp (n, B) int32 or None, (distance rounds, closest-point rounds)).  out_ptr / out_idx: the same
+    edges by the vertex they leave (rounds then only look at values whose in-neighbours moved)."""
+    global sssp_last_ms
+    if out_ptr is None or SSSP_FULL_SWEEPS:
+        out_ptr = out_idx = None
+    else:
+        out_ptr = np.ascontiguousarray(out_ptr, dtype=np.int64)
+        out_idx = np.ascontiguousarray(out_idx, dtype=np.int32)
+        if len(out_ptr) != len(in_ptr) or len(out_idx) != len(in_idx):
+            raise GlxError('sssp: the out-edge lists do not match the in-edge lists')
+    in_ptr = np.ascontiguousarray(in_ptr, dtype=np.int64)
+    in_idx = np.ascontiguousarray(in_idx, dtype=np.int32)
+    in_cost = np.ascontiguousarray(in_cost, dtype=np.float64)
+    src_ptr = np.ascontiguousarray(src_ptr, dtype=np.int64)
+    src_idx = np.ascontiguousarray(src_idx, dtype=np.int32)
+    src_val = np.ascontiguousarray(src_val, dtype=np.float64)
+    n, B = len(in_ptr) - 1, len(src_ptr) - 1
+    if n < 1 or B < 1 or len(in_idx) != len(in_cost) or len(src_idx) != len(src_val):
+        raise GlxError('sssp: inconsistent array lengths')
+    dist = np.empty((n, B), dtype=np.float64)
+    cp = np.empty((n, B), dtype=np.int32) if return_cp else None
+    rounds = (C.c_int64 * 2)(0, 0)
+    ms = (C.c_double * 4)(0, 0, 0, 0)
+    check(load().glx_sssp(n, len(in_idx), _ptr(in_ptr), _ptr(in_idx), _ptr(in_cost), _ptr(out_ptr), _ptr(out_idx), B, _ptr(src_ptr),
+                          _ptr(src_idx), _ptr(src_val), float(max_dist), GLX_SSSP_HOPF_LAX if hopf_lax else GLX_SSSP_PLAIN, _ptr(dist),
+                          _ptr(cp), rounds, ms, _dev(device)), 'glx_sssp')
+    sssp_last_ms = tuple(ms)
+    return dist, cp, (int(rounds[0]), int(rounds[1]))
 
 
 def host_row_sums(W):

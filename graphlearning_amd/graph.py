@@ -1,10 +1,15 @@
 """Graph object: the part of reference graphlearning/graph.py on the hot path
 (`graph.__init__` :25-67, `degree_vector` :108-122, `degree_matrix` :210-233,
-`laplacian` :469-513).  The reference's `__ccode_init__` (graph.py:69-84, 0.4-0.6 s per
+`laplacian` :469-513) and its shortest-path family (`dijkstra` :1077-1175, `dijkstra_hl`
+:916-997, `distance` :999-1046, `distance_matrix` :1048-1075).  The reference's `__ccode_init__` (graph.py:69-84, 0.4-0.6 s per
 construction at 70k nodes, never used by this path) is not executed."""
 import sys
 import numpy as np
 from scipy import sparse
+
+
+# distance_matrix: values (vertices x sources) of one batched device call -- 2^26 doubles are 512 MiB on the device and in the result
+_DISTANCE_MATRIX_VALUES = 1 << 26
 
 
 class graph:
@@ -157,6 +162,149 @@ class graph:
         self.plaplace_iters = _hip.lp_iterate(uu, ul, self.J, self.I, self.V, bdy_set, bdy_val, p, int(max_num_it), float(tol),
                                               device=device)
         return (uu + ul) / 2
+
+    def neighbors(self, i, return_weights=False):
+        """Neighbours of vertex i (and the weights of the edges to them), reference graph.py:124-151."""
+        N = self.weight_matrix[i, :].nonzero()[1]
+        N = N[N != i]
+        if return_weights:
+            return N, self.weight_matrix[i, N].toarray().flatten()
+        return N
+
+    def _in_edges(self):
+        """The edges the reference's Dijkstra walks (`sparse.find` in its __ccode_init__, graph.py:72: explicit zeros dropped; the
+        loop itself skips j == i), listed by the vertex they ENTER: (in_ptr (n+1,), in_idx = the vertex i each edge leaves, V, 1/V),
+        and the same edges by the vertex they LEAVE (out_ptr, out_idx: the device marks along them which values a lowered value
+        can still lower).  Built once per graph object, like the arrays of __ccode_init__.  Unlike the reference's `K`
+        (graph.py:75-76) the pointers are right when a vertex has no entry."""
+        if getattr(self, '_sssp_edges', None) is None:
+            n = self.num_nodes
+            Wc = self.weight_matrix.tocsc(copy=True)
+            Wc.sum_duplicates()
+            col = np.repeat(np.arange(n, dtype=np.int32), np.diff(Wc.indptr))
+            keep = (Wc.data != 0) & (Wc.indices != col)
+            V = np.ascontiguousarray(Wc.data[keep], dtype=np.float64)
+            if not np.all(V >= 0):
+                raise ValueError('graph.dijkstra: the weight matrix has a negative or NaN entry')
+            in_ptr = np.concatenate(([0], np.cumsum(np.bincount(col[keep], minlength=n)))).astype(np.int64)
+            with np.errstate(divide='ignore'):
+                Vinv = 1 / V
+            Wr = self.weight_matrix.copy()
+            Wr.sum_duplicates()
+            row = np.repeat(np.arange(n, dtype=np.int32), np.diff(Wr.indptr))
+            keep_r = (Wr.data != 0) & (Wr.indices != row)
+            out_ptr = np.concatenate(([0], np.cumsum(np.bincount(row[keep_r], minlength=n)))).astype(np.int64)
+            self._sssp_edges = (in_ptr, np.ascontiguousarray(Wc.indices[keep], dtype=np.int32), V, Vinv, out_ptr,
+                                np.ascontiguousarray(Wr.indices[keep_r], dtype=np.int32))
+        return self._sssp_edges
+
+    def _dijkstra_batch(self, problems, f=1, max_dist=np.inf, return_cp=False, reciprocal_weights=False, hopf_lax=False, device=None):
+        """B shortest-path problems on this graph in one device call (glx_sssp): `problems` is a list of (bdy_set, bdy_val) in the
+        standard form.  Returns dist (n, B) float64, cp (n, B) int32 or None; every column equals the single call bit for bit."""
+        from . import _hip
+        n = self.num_nodes
+        f_scalar = None
+        if type(f) != np.ndarray:           # the reference's `f = np.ones((n,))*f`: every vertex holds fl(1.0 * f) = float64(f)
+            f_scalar = np.float64(f)
+            f = np.reshape(f_scalar, (1,))
+        else:
+            f = np.ascontiguousarray(f, dtype=np.float64)
+            if f.shape != (n,):
+                raise ValueError('graph.dijkstra: f has shape %s, expected (%d,)' % (f.shape, n))
+        if not np.all(f >= 0):
+            raise ValueError('graph.dijkstra: f has a negative or NaN entry')
+        max_dist = float(max_dist)
+        if max_dist != max_dist:
+            raise ValueError('graph.dijkstra: max_dist is NaN')
+        src_ptr, src_idx, src_val = [0], [], []
+        for bdy_set, bdy_val in problems:
+            bdy_set = np.ascontiguousarray(bdy_set, dtype=np.int64).ravel()
+            bdy_val = np.ascontiguousarray(bdy_val, dtype=np.float64).ravel()
+            if len(bdy_set) != len(bdy_val):
+                raise ValueError('graph.dijkstra: %d boundary values for %d boundary vertices' % (len(bdy_val), len(bdy_set)))
+            if len(bdy_set) and (bdy_set.min() < 0 or bdy_set.max() >= n):
+                raise ValueError('graph.dijkstra: boundary index out of range')
+            if len(np.unique(bdy_set)) != len(bdy_set):
+                raise ValueError('graph.dijkstra: bdy_set lists a vertex twice (the reference\'s heap does not survive that)')
+            if not np.all(bdy_val >= 0):
+                raise ValueError('graph.dijkstra: bdy_val has a negative or NaN entry')
+            src_idx.append(bdy_set.astype(np.int32))
+            src_val.append(bdy_val)
+            src_ptr.append(src_ptr[-1] + len(bdy_set))
+        in_ptr, in_idx, V, Vinv, out_ptr, out_idx = self._in_edges()
+        # c_ij = W[i,j] * f[i]: f at the vertex the edge leaves (hjsolvers.cpp:210); a constant f needs no gather, and w * 1.0 is w
+        Vx = Vinv if reciprocal_weights else V
+        cost = Vx * f[in_idx] if f_scalar is None else (Vx if f_scalar == 1 else Vx * f_scalar)
+        dist, cp, rounds = _hip.sssp(in_ptr, in_idx, cost, np.array(src_ptr, dtype=np.int64),
+                                     np.concatenate(src_idx) if src_idx else np.zeros(0, dtype=np.int32),
+                                     np.concatenate(src_val) if src_val else np.zeros(0), max_dist=max_dist, hopf_lax=hopf_lax,
+                                     return_cp=return_cp, device=device, out_ptr=out_ptr, out_idx=out_idx)
+        self.dijkstra_rounds = rounds
+        return dist, cp
+
+    def _dijkstra_one(self, bdy_set, bdy_val, f, max_dist, return_cp, reciprocal_weights, hopf_lax, device):
+        from . import utils
+        bdy_set, bdy_val = utils._boundary_handling(bdy_set, bdy_val)
+        dist, cp = self._dijkstra_batch([(bdy_set, bdy_val)], f=f, max_dist=max_dist, return_cp=return_cp,
+                                        reciprocal_weights=reciprocal_weights, hopf_lax=hopf_lax, device=device)
+        if return_cp:
+            return np.ascontiguousarray(dist[:, 0]), np.ascontiguousarray(cp[:, 0])
+        return np.ascontiguousarray(dist[:, 0])
+
+    def dijkstra(self, bdy_set, bdy_val=0, f=1, max_dist=np.inf, return_cp=False, reciprocal_weights=False, device=None):
+        """Distance function u(x) = min over boundary vertices i of g_i + d(x_i, x), d the cheapest path with edge costs
+        w_ij f_i (1/w_ij with `reciprocal_weights`), and optionally the closest boundary vertex (reference graph.py:1077-1175,
+        dijkstra_main of its C extension).  Runs on the GPU as label-correcting rounds whose fixed point is the heap's result
+        bit for bit (glx_sssp; the argument heads csrc/sssp.hip).  Returns dist_func float64 (n,), and cp int32 (n,) with
+        `return_cp`.  Where the reference's documentation and code differ this follows the documentation: vertices farther
+        than `max_dist` hold inf and cp -1.  Where several boundary vertices tie for closest, cp is the smallest index among
+        them (the reference's choice depends on its heap's history).  Refused with ValueError: a vertex listed twice in
+        `bdy_set`; a negative or NaN `f`, `bdy_val` or weight."""
+        return self._dijkstra_one(bdy_set, bdy_val, f, max_dist, return_cp, reciprocal_weights, False, device)
+
+    def dijkstra_hl(self, bdy_set, bdy_val=0, f=1, max_dist=np.inf, return_cp=False, device=None):
+        """Dijkstra's algorithm with the Hopf-Lax relaxation u_j = (c + sqrt(c^2 + 4 u_i^2)) / 2, c = w_ij f_i (reference
+        graph.py:916-997, dijkstra_hl_main), on the GPU; conventions as in `dijkstra`."""
+        return self._dijkstra_one(bdy_set, bdy_val, f, max_dist, return_cp, False, True, device)
+
+    def distance(self, i, j, return_path=False, return_distance_vector=False):
+        """Shortest-path distance between vertices i and j with edge costs 1/w, optionally a shortest path (from j back to i) and the
+        distance vector to i (reference graph.py:999-1046; the path walk is the reference's host loop)."""
+        v = self.dijkstra([i], reciprocal_weights=True)
+        d = v[j]
+        if return_path:
+            if not np.isfinite(d):
+                raise ValueError('graph.distance: no path from %d to %d' % (i, j))
+            p = j
+            path = [p]
+            while p != i:
+                nn, w = self.neighbors(p, return_weights=True)
+                k = np.argmin(v[nn] + w ** -1)
+                p = nn[k]
+                path += [p]
+            path = np.array(path)
+            if return_distance_vector:
+                return d, path, v
+            return d, path
+        if return_distance_vector:
+            return d, v
+        return d
+
+    def distance_matrix(self, centered=False):
+        """All-pairs shortest-path distances with edge costs 1/w (reference graph.py:1048-1075: n calls of `distance`); here the
+        sources ride as the columns of a few batched device calls, every row equal to the single call bit for bit."""
+        n = self.num_nodes
+        T = np.zeros((n, n))
+        batch = max(1, min(n, _DISTANCE_MATRIX_VALUES // n))
+        zero = np.zeros(1)
+        for lo in range(0, n, batch):
+            hi = min(n, lo + batch)
+            dist, _ = self._dijkstra_batch([(np.array([s]), zero) for s in range(lo, hi)], reciprocal_weights=True)
+            T[lo:hi, :] = dist.T
+        if centered:
+            J = np.eye(n) - (1 / n) * np.ones((n, n))
+            T = -0.5 * J @ T @ J
+        return T
 
     def subgraph(self, ind):
         W = self.weight_matrix

@@ -1191,6 +1191,38 @@ class randomwalk(ssl):
         return [M * np.ascontiguousarray(x[:, j * k:(j + 1) * k]) for j in range(len(trials))]
 
 
+class graph_nearest_neighbor(ssl):
+    def __init__(self, W=None, class_priors=None, D=None, alpha=1):
+        """Graph (geodesic) nearest-neighbour classifier (reference ssl.py:1511-1567): every vertex takes the label of the
+        labelled vertex closest in graph distance; with class priors, one-vs-rest distances to each class (a dissimilarity)
+        go through the volume-constrained projection.  D: (n, n) sparse matrix of neighbour distances, reweights the edge
+        costs by (distance to the farthest neighbour / its maximum)**alpha.  The distances and closest points come from
+        graph.dijkstra on the GPU."""
+        super().__init__(W, class_priors)
+        self.alpha = alpha
+        if class_priors is not None:
+            self.onevsrest = True
+            self.similarity = False
+        if D is None:
+            self.f = 1
+        else:
+            d = D.max(axis=1).toarray().flatten()
+            self.f = (d / np.max(d)) ** alpha
+        self.accuracy_filename = '_graph_nearest_neighbor_alpha%.2f' % (self.alpha)
+        self.name = 'Graph NN (alpha=%.2f)' % (self.alpha)
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        if self.onevsrest:
+            u = self.graph.dijkstra(train_ind[train_labels], bdy_val=0, f=self.f, device=self.device)
+        else:
+            _, l = self.graph.dijkstra(train_ind, bdy_val=np.zeros_like(train_ind), f=self.f, return_cp=True, device=self.device)
+            u = np.zeros(l.shape)
+            u[train_ind] = train_labels
+            k = len(np.unique(train_labels))
+            u = utils.labels_to_onehot(u[l], k)
+        return u
+
+
 def ssl_accuracy(pred_labels, true_labels, train_ind):
     """Accuracy in percent over nodes outside train_ind with a true label >= 0
     (reference ssl.py:1795-1834: `100*np.mean(pred[mask] == true[mask])` over the masked arrays).  The same number from

@@ -172,6 +172,28 @@ int glx_ball_result_to_csr(const glx_ball_result* res, int kernel, double epsilo
 int glx_ball_result_destroy(glx_ball_result* res);
 int glx_ball_stats(double stats[8]);
 
+/* ---- shortest paths: graph.dijkstra / graph.dijkstra_hl (csrc/sssp.hip) ------------------------------------------------------------
+ * Replaces dijkstra_main / dijkstra_hl_main of the reference's C extension (c_code/hjsolvers.cpp:117-227) by label-correcting rounds
+ * on the device whose fixed point is the heap's result bit for bit (the argument heads csrc/sssp.hip).
+ * The graph arrives as its IN-edge lists: vertex j's entries in_idx[in_ptr[j] .. in_ptr[j+1]) are the vertices i with an edge i -> j,
+ * in_cost the costs c_ij = fl(W[i,j] * f[i]) >= 0 (self entries and explicit zeros of W already removed; +inf allowed).
+ * B >= 1 independent problems on that graph: problem b's sources are src_idx[src_ptr[b] .. src_ptr[b+1]) with boundary values
+ * src_val >= 0; a vertex listed twice in one problem is refused.  form: the relaxation, GLX_SSSP_PLAIN fl(a + c) or
+ * GLX_SSSP_HOPF_LAX (c + sqrt(c*c + 4*a*a))/2.  A vertex is relaxed from i only while u_i <= max_dist.
+ * dist (n, B) fp64, vertex-major: the distances, +inf where they exceed max_dist or nothing is reached.  cp (n, B) int32 or NULL: the
+ * smallest source index reaching the vertex along tight edges, -1 where dist is +inf.  rounds_out[2] (or NULL): rounds of the distance
+ * and of the closest-point iteration, the idle last round included.  n * B <= 2^31.  All pointers are host pointers.
+ * out_ptr / out_idx (or NULL): the same edges listed by the vertex they LEAVE (out_idx[out_ptr[i] .. out_ptr[i+1]) = the vertices j
+ * with an edge i -> j).  With them a round only looks at values one of whose in-neighbours was lowered in the round before; without
+ * them every round looks at every value (same results, for measurement).  ms_out[4] (or NULL): host milliseconds of the uploads, the
+ * distance rounds, the closest-point rounds and the downloads. */
+#define GLX_SSSP_PLAIN 0
+#define GLX_SSSP_HOPF_LAX 1
+int glx_sssp(int64_t n, int64_t nnz, const int64_t* in_ptr, const int32_t* in_idx, const double* in_cost,
+             const int64_t* out_ptr, const int32_t* out_idx, int B, const int64_t* src_ptr, const int32_t* src_idx,
+             const double* src_val, double max_dist, int form, double* dist, int32_t* cp, int64_t* rounds_out, double* ms_out,
+             int device);
+
 #ifdef __cplusplus
 }
 #endif
