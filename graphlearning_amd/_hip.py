@@ -1013,7 +1013,9 @@ class DistSweep:
 
 
 def nearest_dist(X, idx, device=None):
-    """Distance from every row of X to the nearest of its rows `idx` (glx_nearest_dist: cKDTree(X[idx]).query(X)[0], bit for bit)."""
+    """Distance from every row of X to the nearest of its rows `idx` (glx_nearest_dist: cKDTree(X[idx]).query(X)[0], bit for bit).
+    GlxError for an empty `idx`, an index outside [0, n), more than 6144 features, and for a NaN or an infinity anywhere in X (the
+    reference's cKDTree raises on non-finite data; weightmatrix.epsilon_ball refuses it too)."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2:
         raise GlxError('nearest_dist: X must be (n, d)')

@@ -665,6 +665,9 @@ extern "C" int glx_nearest_dist(const double* X, int64_t n, int d, const int64_t
   GLX_CHECK(X && idx && dist_out && n >= 1 && d >= 1 && m >= 1, GLX_EINVAL, "glx_nearest_dist: bad argument");
   GLX_CHECK((size_t)d * 8 <= 48 * 1024, GLX_EUNSUPPORTED, "glx_nearest_dist: %d features exceed one row of the LDS stage", d);
   for (int64_t j = 0; j < m; ++j) GLX_CHECK(idx[j] >= 0 && idx[j] < n, GLX_EINVAL, "glx_nearest_dist: row %lld out of range", (long long)idx[j]);
+  // non-finite data is refused, as weightmatrix.epsilon_ball refuses it (the reference's cKDTree raises on it)
+  for (int64_t i = 0; i < n * (int64_t)d; ++i)
+    GLX_CHECK(std::isfinite(X[i]), GLX_EINVAL, "glx_nearest_dist: X[%lld, %lld] is not finite", (long long)(i / d), (long long)(i % d));
   GLX_HIP(hipSetDevice(device));
   std::vector<double> R((size_t)m * d);
   for (int64_t j = 0; j < m; ++j) memcpy(R.data() + (size_t)j * d, X + (size_t)idx[j] * d, (size_t)d * 8);

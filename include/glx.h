@@ -321,7 +321,8 @@ int glx_knn_bruteforce(const double* X, int64_t n, int d, int k, int similarity,
                        int64_t* ind_out, double* dist_out, int device);
 /* dist_out[i] = euclidean distance from row i of X (n, d) to the nearest of its rows idx[0 .. m): `cKDTree(X[idx]).query(X)[0]` of
  * graph.reweight(method='properly') (graphlearning/graph.py:455-457), all pairs with cKDTree's accumulation pattern -- the reference's
- * distances bit for bit.  Host arrays. */
+ * distances bit for bit.  Host arrays.  Refused with GLX_EINVAL before anything is launched: an empty idx (m < 1), an index outside
+ * [0, n), a NaN or an infinity anywhere in X (the reference's cKDTree raises on it); with GLX_EUNSUPPORTED: d > 6144. */
 int glx_nearest_dist(const double* X, int64_t n, int d, const int64_t* idx, int64_t m, double* dist_out, int device);
 
 /* same search restricted to the query rows [q_begin, q_end) (rank-local share when the queries are

@@ -426,9 +426,10 @@ def test_page_rank_midsize_vs_oracle(gl, orc):
 
 @pytest.mark.parametrize('dtype', [np.float64, np.float32])
 def test_sweep_project_equals_host_projection(gl, dtype):
-    """glx_sweep_project_iterate with iters = 0 (decision on the device-resident sweep state) against glx_argmax_project on the
-    fetched array (which the g5 golden pins to the reference): labels, weights, error, step count; then
-    the state has become onehot(labels)."""
+    """glx_sweep_project_iterate with iters = 0 (decision on the device-resident sweep state) against the numpy restatement
+    tests/decision_ref.py (which tests/test_decision_host.py pins to the reference) on the same array, and glx_argmax_project
+    against it too: labels, weights, error, step count; then the state has become onehot(labels)."""
+    import decision_ref
     from graphlearning_amd import _hip
     from scipy import sparse
     rng = np.random.default_rng(11)
@@ -438,7 +439,9 @@ def test_sweep_project_equals_host_projection(gl, dtype):
     G = _hip.DeviceGraph(sparse.identity(n, format='csr'), dtype=dtype)
     S = _hip.Sweep(G, C, min_iter=0, max_iter=0, use_hipgraph=False)
     S.set_state(prob, None)
-    ref = _hip.argmax_project(prob.astype(np.float64), priors, np.ones(C), max_steps=10000)
+    ref = decision_ref.volume_label_projection(prob, priors, np.ones(C), True, max_steps=10000)
+    host = _hip.argmax_project(prob, priors, np.ones(C), max_steps=10000)
+    assert host[3] == ref[3] and np.array_equal(host[0], ref[0]) and np.array_equal(host[1], ref[1]) and host[2] == ref[2]
     labels, w, err, steps = S.project(priors, np.ones(C), max_steps=10000, to_onehot=True)
     assert steps == ref[3] and steps > 1
     assert np.array_equal(labels, ref[0]) and np.array_equal(w, ref[1]) and err == ref[2]
@@ -449,7 +452,8 @@ def test_sweep_project_equals_host_projection(gl, dtype):
     none, w2, _, _ = S.project(None, w, max_steps=0, want_labels=False)
     assert none is None and np.array_equal(w2, w)
     lab2, _, _, _ = S.project(None, w, max_steps=0)
-    assert np.array_equal(lab2, _hip.argmax_project(prob.astype(np.float64), None, w, max_steps=0)[0])
+    assert np.array_equal(lab2, decision_ref.predict(prob, w))
+    assert np.array_equal(lab2, _hip.argmax_project(prob, None, w, max_steps=0)[0])
     S.close(); G.close()
 
 
