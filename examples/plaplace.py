@@ -1,7 +1,8 @@
 """Mirrors reference examples/plaplace.py: p-Laplace interpolation of boundary values on a random
 geometric graph, the epsilon-ball graph of the reference example (weightmatrix.epsilon_ball, built on
 the GPU).  fast=False selects the Jacobi iteration of the reference's C extension, which runs on the
-GPU; the reference's default fast=True is a sequential Gauss-Seidel sweep and is not provided."""
+GPU.  The reference's default fast=True is an in-order Gauss-Seidel sweep; its exact parallel form (levels, as for graph.amle:
+examples/amle.py) exists in the library but plaplace(fast=True) is not switched on yet."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -154,6 +154,8 @@ _SIGNATURES = {
     'glx_ball_result_destroy': [_vp],
     'glx_ball_stats': [_f64p],
     'glx_sssp': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp, _i64p, _f64p, C.c_int],
+    'glx_lip_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_double,
+                        _vp, _vp, _vp, _vp, C.c_int, C.c_int],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1098,6 +1100,33 @@ def sssp(in_ptr, in_idx, in_cost, src_ptr, src_idx, src_val, max_dist=np.inf, ho
                           _ptr(cp), rounds, ms, _dev(device)), 'glx_sssp')
     sssp_last_ms = tuple(ms)
     return dist, cp, (int(rounds[0]), int(rounds[1]))
+
+
+def lip_iterate(n, nbr, row, W, ind, val, weighted, alpha, beta, T, tol, device=None, want_errors=False, small_level=-1):
+    """In-order Gauss-Seidel sweeps of the reference's lip_iterate on the GPU (glx_lip_iterate, csrc/lip.hip): n vertices, the entry
+    arrays as the reference hands them over (nbr = graph.J, row = graph.I, W = graph.V), the shared boundary vertices `ind` and their
+    values `val` (m, B).  Returns (u (n, B) float64, sweeps done per column (B,) int64, plan = (levels, launches per sweep, launches
+    enqueued in all), errors (T, B) or None: rows a column did not run hold NaN).  small_level: a plan override for measurements --
+    levels of at most that many vertices ride in merged launches (0: none; -1: the library's constant); the result does not depend on it."""
+    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+    row = np.ascontiguousarray(row, dtype=np.int32)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    ind = np.ascontiguousarray(ind, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    if val.ndim != 2 or val.shape[0] != len(ind) or nbr.ndim != 1 or len(nbr) != len(row) or len(nbr) != len(W) or ind.ndim != 1:
+        raise GlxError('lip_iterate: inconsistent array shapes')
+    n, B, T = int(n), int(val.shape[1]), int(T)
+    if n < 1 or B < 1 or T < 0:
+        raise GlxError('lip_iterate: bad sizes (n=%d B=%d T=%d)' % (n, B, T))
+    u = np.empty((n, B), dtype=np.float64)
+    iters = np.zeros(B, dtype=np.int64)
+    plan = (C.c_int64 * 3)(0, 0, 0)
+    errs = np.full((T, B), np.nan) if want_errors else None
+    check(load().glx_lip_iterate(n, len(nbr), _ptr(nbr), _ptr(row), _ptr(W), B, len(ind), _ptr(ind), _ptr(val), 1 if weighted else 0,
+                                 float(alpha), float(beta), T, float(tol), _ptr(u), _ptr(iters), plan, _ptr(errs), int(small_level),
+                                 _dev(device)),
+          'glx_lip_iterate')
+    return u, iters, (int(plan[0]), int(plan[1]), int(plan[2])), errs
 
 
 def host_row_sums(W):

@@ -140,13 +140,15 @@ class graph:
         """Game-theoretic p-Laplace equation with Dirichlet data (reference graph.py:1177-1278).
         `fast=False` -- the Jacobi iteration of upper / lower barriers, lp_iterate_main of the
         reference's C extension -- runs on the GPU (glx_lp_iterate) and returns (uu+ul)/2 like the
-        reference.  The reference's default `fast=True` is a Gauss-Seidel sweep (lip_iterate_main,
-        c_code/lp_iterate.cpp:127-180): every vertex reads values updated earlier in the same sweep,
-        an inherently sequential recurrence that has no parallel form with the same iterates."""
+        reference.  The reference's default `fast=True` is an in-order Gauss-Seidel sweep (lip_iterate_main,
+        c_code/lp_iterate.cpp:129-187) with alpha = 1/(p-1), beta = 1-alpha.  Such a sweep does have an exact parallel form, the
+        level schedule of a sparse triangular solve, and the device routine behind `graph.amle` (glx_lip_iterate) runs it with
+        these arguments bit for bit; `fast=True` itself is not switched on yet and is refused rather than answered by another
+        iteration."""
         from . import _hip, utils
         if fast:
-            raise NotImplementedError('graph.plaplace(fast=True) is a sequential Gauss-Seidel sweep in the reference; '
-                                      'pass fast=False for the Jacobi iteration, which runs on the GPU')
+            raise NotImplementedError('graph.plaplace(fast=True) is not switched on yet (its in-order Gauss-Seidel sweep runs on the GPU as '
+                                      '_hip.lip_iterate with alpha=1/(p-1), beta=1-alpha); pass fast=False for the Jacobi iteration')
         if getattr(self, 'I', None) is None:
             self.__ccode_init__()
         n = self.num_nodes
@@ -162,6 +164,74 @@ class graph:
         self.plaplace_iters = _hip.lp_iterate(uu, ul, self.J, self.I, self.V, bdy_set, bdy_val, p, int(max_num_it), float(tol),
                                               device=device)
         return (uu + ul) / 2
+
+    def _amle_entries(self):
+        """The arrays of __ccode_init__ checked for graph.amle: every weight >= 0 (NaN refused), and which vertices have an entry."""
+        if getattr(self, 'I', None) is None:
+            self.__ccode_init__()
+        if not np.all(self.V >= 0):
+            raise ValueError('graph.amle: the weight matrix has a negative or NaN entry')
+        return np.bincount(self.I, minlength=self.num_nodes) > 0
+
+    def _amle_batch(self, bdy_set, vals, tol=1e-5, max_num_it=1000, weighted=True, prog=False, device=None, small_level=-1):
+        """B AMLE problems that share the boundary vertices `bdy_set`, one per column of `vals` (m, B), in one device call
+        (glx_lip_iterate): returns u (n, B) float64; every column equals its single `amle` call bit for bit, and stops on its own.
+        Sets amle_iters (sweeps done per column), amle_levels and amle_plan (levels, launches per sweep, launches enqueued in all).
+        With `prog` the reference's progress lines are printed AFTER the solve, from the errors the host read while it ran, one
+        column after another (the order of the reference's class-by-class calls).  small_level: plan override for measurements
+        (_hip.lip_iterate); the result does not depend on it."""
+        from . import _hip, utils
+        n = self.num_nodes
+        bdy_set, _ = utils._boundary_handling(bdy_set, 0)
+        bdy_set = np.ascontiguousarray(bdy_set, dtype=np.int64).ravel()
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if vals.ndim != 2 or vals.shape[0] != len(bdy_set) or vals.shape[1] < 1:
+            raise ValueError('graph.amle: boundary values of shape %s for %d boundary vertices' % (vals.shape, len(bdy_set)))
+        if len(bdy_set) and (bdy_set.min() < 0 or bdy_set.max() >= n):
+            raise ValueError('graph.amle: boundary index out of range')
+        if not np.all(np.isfinite(vals)):
+            raise ValueError('graph.amle: bdy_val has a non-finite entry')
+        tol = float(tol)
+        if not np.isfinite(tol):
+            raise ValueError('graph.amle: tol is not finite')
+        T = int(float(max_num_it))
+        if T > (1 << 24):
+            raise ValueError('graph.amle: max_num_it=%r above the supported 2^24 sweeps' % (max_num_it,))
+        T = max(T, 0)                    # `for(it=0;it<T;it++)`: a negative T sweeps nothing
+        has_entry = self._amle_entries()
+        free = ~has_entry
+        free[bdy_set] = False
+        if free.any():
+            raise ValueError('graph.amle: vertex %d is not on the boundary and has no stored entry (the reference reads another '
+                             'vertex\'s entry there)' % int(np.where(free)[0][0]))
+        u, iters, plan, errs = _hip.lip_iterate(n, self.J, self.I, self.V, bdy_set.astype(np.int32), vals, weighted, 0.0, 1.0, T, tol,
+                                                device=device, want_errors=bool(prog), small_level=small_level)
+        self.amle_iters = iters
+        self.amle_levels = plan[0]
+        self.amle_plan = plan
+        if prog:                         # the reference's lines (lp_iterate.cpp:156, :180), one column after another
+            for b in range(vals.shape[1]):
+                for it in range(int(iters[b])):
+                    sys.stdout.write('Iter=%d, err=%.15f\n' % (it, errs[it, b]))
+            sys.stdout.flush()
+        return u
+
+    def amle(self, bdy_set, bdy_val, tol=1e-5, max_num_it=1000, weighted=True, prog=False, device=None):
+        """Absolutely minimal Lipschitz extension of the boundary values: the solution of the graph infinity-Laplace equation
+        min_j w_ij (u_i - u_j) + max_j w_ij (u_i - u_j) = 0 off the boundary (reference graph.py:1281-1332).  The reference's
+        in-order Gauss-Seidel sweeps (lip_iterate_weighted_main: 30 bisection passes per vertex; `weighted=False`,
+        lip_iterate_main: the midpoint of the smallest and largest neighbouring value) run on the GPU level by level
+        (glx_lip_iterate; the argument heads csrc/lip_plan.h) and give the reference's iterates bit for bit.  Returns u float64
+        (n,); sets amle_iters (sweeps done) and amle_levels.  With `prog` the reference's progress lines are printed after the solve
+        has finished, not while it runs.  A vertex listed twice in `bdy_set` takes its last value.  Refused
+        with ValueError: a vertex off the boundary without a stored entry (the reference reads another vertex's entry, or past
+        its arrays), a negative or NaN weight, a non-finite `bdy_val` or `tol`."""
+        from . import utils
+        bdy_set, bdy_val = utils._boundary_handling(bdy_set, bdy_val)
+        bdy_val = np.asarray(bdy_val, dtype=np.float64).ravel()
+        u = self._amle_batch(bdy_set, bdy_val[:, None], tol=tol, max_num_it=max_num_it, weighted=weighted, prog=prog, device=device)
+        self.amle_iters = int(self.amle_iters[0])
+        return np.ascontiguousarray(u[:, 0])
 
     def neighbors(self, i, return_weights=False):
         """Neighbours of vertex i (and the weights of the edges to them), reference graph.py:124-151."""

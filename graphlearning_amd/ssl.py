@@ -217,8 +217,12 @@ class ssl:
         if self.onevsrest:
             unique_labels = np.unique(train_labels)
             self.prob = np.zeros((self.graph.num_nodes, len(unique_labels)))
-            for i, l in enumerate(unique_labels):
-                self.prob[:, i] = self._fit(train_ind, train_labels == l)
+            cols = self._fit_onevsrest(train_ind, train_labels, unique_labels)
+            if cols is not None:             # the learner solved all classes as the columns of one call
+                self.prob[:, :] = cols
+            else:
+                for i, l in enumerate(unique_labels):
+                    self.prob[:, i] = self._fit(train_ind, train_labels == l)
         else:
             pending = self._speculate_key()
             # a speculative fit runs on operators cached for the matrix's PREVIOUS content: whatever it changes in the model
@@ -335,6 +339,12 @@ class ssl:
     def _trial_batch_size(self, labels):
         """How many trials ssl_trials hands to _fit_batch at once (1 = one by one)."""
         return 1
+
+    def _fit_onevsrest(self, train_ind, train_labels, unique_labels):
+        """Hook of the one-vs-rest loop: a learner whose classes can ride as the columns of one device call returns the (n, classes)
+        scores, column i what `_fit(train_ind, train_labels == unique_labels[i])` returns bit for bit; None (the default): the
+        loop calls `_fit` class by class."""
+        return None
 
     def _fit_batch(self, trials):
         """Fit several (train_ind, train_labels) pairs on the same graph in one device call and
@@ -1220,6 +1230,35 @@ class graph_nearest_neighbor(ssl):
             u[train_ind] = train_labels
             k = len(np.unique(train_labels))
             u = utils.labels_to_onehot(u[l], k)
+        return u
+
+
+class amle(ssl):
+    def __init__(self, W=None, class_priors=None, tol=1e-3, max_num_it=1e5, weighted=False, prog=False):
+        """Semi-supervised learning by the absolutely minimal Lipschitz extension (reference ssl.py:1569-1614): one-vs-rest, class
+        l's score is graph.amle of the 0/1 indicator of its labelled vertices; p-Laplace learning with p = infinity.
+        `weighted=False` uses the graph as a 0/1 adjacency (the midpoint form of the sweep).  All classes are solved as the columns
+        of one device call (graph._amle_batch); every column stops on its own, as the reference's class-by-class calls do."""
+        super().__init__(W, class_priors)
+        self.tol = tol
+        self.max_num_it = max_num_it
+        self.weighted = weighted
+        self.prog = prog
+        self.onevsrest = True
+        self.accuracy_filename = '_amle'
+        if not self.weighted:
+            self.accuracy_filename += '_unweighted'
+        self.name = 'AMLE'
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        return self.graph.amle(train_ind, train_labels, tol=self.tol, max_num_it=self.max_num_it, weighted=self.weighted,
+                               prog=self.prog, device=self.device)
+
+    def _fit_onevsrest(self, train_ind, train_labels, unique_labels):
+        vals = (train_labels[:, None] == unique_labels[None, :]).astype(np.float64)      # `train_labels == l` cast like the reference's bdy_val
+        u = self.graph._amle_batch(train_ind, vals, tol=self.tol, max_num_it=self.max_num_it, weighted=self.weighted, prog=self.prog,
+                                   device=self.device)
+        self.num_iter = [int(i) for i in self.graph.amle_iters]
         return u
 
 

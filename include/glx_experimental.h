@@ -194,6 +194,27 @@ int glx_sssp(int64_t n, int64_t nnz, const int64_t* in_ptr, const int32_t* in_id
              const double* src_val, double max_dist, int form, double* dist, int32_t* cp, int64_t* rounds_out, double* ms_out,
              int device);
 
+/* ---- in-order Gauss-Seidel sweeps: graph.amle / ssl.amle (csrc/lip.hip, csrc/lip_plan.h) ---------------------------------------------
+ * lip_iterate_main (weighted = 0) and lip_iterate_weighted_main (weighted != 0) of the reference's C extension
+ * (c_code/lp_iterate.cpp:129-259) bit for bit: the sequential sweep in vertex order runs as the levels of its dependence pattern,
+ * a launch per level or one workgroup over a run of small levels.
+ * The graph arrives as the reference hands it over: M stored entries sorted by vertex, row[e] the vertex, nbr[e] its neighbour, W[e] >= 0
+ * the weight, the order inside a vertex's block the caller's (it decides the rounding).  B >= 1 columns share the m boundary vertices
+ * ind (a vertex listed twice takes its last value); val (m, B) row-major are their values per column.  u starts at zero off the boundary.
+ * Unweighted: ne = alpha*sumu/deg + beta*(minu + maxu)/2 (graph.amle: alpha 0, beta 1; graph.plaplace(fast=True): alpha 1/(p-1),
+ * beta 1-alpha); weighted: 30 bisection passes per vertex, alpha and beta unused.  At most T <= 2^24 sweeps; a column stops on its own
+ * after the sweep `it` with err < tol && it > 20 and is frozen from then on.
+ * u (n, B) row-major: the result.  iters_out[B] (or NULL): sweeps done per column.  plan_out[3] (or NULL): levels, launches per
+ * sweep, launches enqueued in all.  err_hist (T, B) or NULL: err of sweep `it`, column b at [it * B + b] for the sweeps the column
+ * ran (other entries are left alone).  small_level: a plan override for measurements -- levels of at most that many vertices are merged
+ * into single-workgroup launches (0: none are, every level is a launch of its own; < 0: the library's constant).  The result does not
+ * depend on it.  All pointers are host pointers.
+ * GLX_EINVAL: a null argument, B < 1, an index out of range, entries not sorted by vertex, a negative or NaN weight, a vertex that is
+ * not on the boundary and has no stored entry (the reference reads another vertex's entry, or past the arrays, there). */
+int glx_lip_iterate(int64_t n, int64_t M, const int32_t* nbr, const int32_t* row, const double* W, int B, int64_t m, const int32_t* ind,
+                    const double* val, int weighted, double alpha, double beta, int64_t T, double tol, double* u, int64_t* iters_out,
+                    int64_t* plan_out, double* err_hist, int small_level, int device);
+
 #ifdef __cplusplus
 }
 #endif
