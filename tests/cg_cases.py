@@ -1,0 +1,216 @@
+"""The one table of tolerance-mode conjugate-gradient cases: tests/test_gpu_cg_wide.py runs every one of them on the device,
+tests/test_cg_ref_host.py asserts for every one of them -- without a GPU -- that its operator is definite, that no residual norm of
+its reference run comes near `tol`, and that the reference stops after the same number of iterations in the case's own number
+format and in long double.  The device's iteration counts are therefore compared exactly, on every case.
+
+A case is a dict; `build(case)` makes the system, `reference(case)` solves it with tests/cg_ref.py (cached: the long-double run
+and the run in the case's format).  SEEDS holds, per case id, the seed at which the case's smallest stop margin is at least 1e-2
+(the first such seed counting up from 0; `python tests/cg_cases.py` prints the table again).
+"""
+import functools
+import numpy as np
+import cg_ref
+
+STOP_BAND = 1e-3           # ssl.AUTO_STOP_BAND: a stop decision nearer to tol than this (relative) counts as undecided
+MIN_MARGIN = 1e-2          # what the seeds are chosen for
+TOL = {'f64': 1e-9, 'f32': 1e-3}
+
+WIDTHS = [1, 2, 3, 4, 5, 8, 9, 16, 17, 20, 21, 24, 25, 28, 29, 32, 33, 37, 41, 64, 65, 100, 127, 128, 129, 200, 240, 252, 253, 256]
+ROWS_N = [1, 2, 63, 64, 65, 127, 128, 129, 257, 517]
+CAPS = [0, 1, 3, 4, 15, 16, 17, 19, 20, 21, 24, 36]
+
+
+def _case(id, **kw):
+    c = dict(id=id, op='lap', n=300, tau=1.0, C=3, dt='f64', tol=None, max_iter=100000, group_cols=None, masks=False, x0=False,
+             zero_cols=(), rhs='normal', keep_order=True, api='cg', out_scale=False)
+    c.update(kw)
+    if c['tol'] is None:
+        c['tol'] = TOL[c['dt']]
+    if c['group_cols'] is None:
+        c['group_cols'] = c['C']
+    return c
+
+
+def _table():
+    t = []
+    for dt in ('f64', 'f32'):
+        for C in WIDTHS:
+            t.append(_case('width-C%d-%s' % (C, dt), C=C, dt=dt))
+        for n in ROWS_N:
+            for C in (3, 17, 100):
+                t.append(_case('rows-n%d-C%d-%s' % (n, C, dt), n=n, C=C, dt=dt))
+        for keep in (False, True):
+            for C in (5, 21):
+                t.append(_case('renum-%s-C%d-%s' % ('keep' if keep else 'renumbered', C, dt), n=4200, C=C, dt=dt, keep_order=keep))
+        for C in (3, 21):
+            t.append(_case('x0-C%d-%s' % (C, dt), C=C, dt=dt, x0=True))
+        for C, z in ((5, 2), (21, 17)):
+            t.append(_case('zerocol-C%d-%s' % (C, dt), C=C, dt=dt, zero_cols=(z,)))
+        t.append(_case('zerosystem-%s' % dt, C=8, group_cols=4, dt=dt, zero_cols=(0, 1, 2, 3), api='groups'))
+        t.append(_case('eigenvector-%s' % dt, C=5, dt=dt, tau=0.5, rhs='eig'))
+        for tol in (2.0, 1.0):
+            for x0 in (False, True):
+                t.append(_case('tol%g-%s-%s' % (tol, 'x0' if x0 else 'zero', dt), C=5, dt=dt, tol=tol, x0=x0))
+        for gc in (1, 3, 10):
+            for ng in (2, 7, 24, 32):
+                if gc * ng > 256:
+                    continue
+                for masks in (False, True):
+                    t.append(_case('stack-%dx%d-%s-%s' % (ng, gc, 'masks' if masks else 'plain', dt), C=gc * ng, group_cols=gc, dt=dt,
+                                   masks=masks, rhs='spread', api='groups'))
+        for n in (300, 4200):
+            for scale in (False, True):
+                t.append(_case('sparse-rhs-n%d-%s-%s' % (n, 'scaled' if scale else 'plain', dt), n=n, C=12, group_cols=3, dt=dt, masks=True,
+                               rhs='rows', api='rows', out_scale=scale, keep_order=False))
+    for C in (3, 17):           # crosses the doubling of rows_per_block (> 262 144 rows) and grp > 32 (> 2048 SpMM workgroups)
+        t.append(_case('large-C%d-f64' % C, op='banded', n=300000, C=C, tol=1e-12, max_iter=6, keep_order=False))
+    for cap in CAPS:
+        t.append(_case('cap-%d-f64' % cap, C=7, max_iter=cap))
+    # one DeviceGraph, width / number of systems / cap changing between the solves (the order of the mirror test)
+    for j, (cap, C, gc) in enumerate(((500, 240, 10), (40, 17, 17), (500, 100, 50), (7, 240, 10), (500, 17, 17), (19, 100, 100), (3, 34, 17))):
+        t.append(_case('sequence-%d-cap%d-C%d-by%d-f64' % (j, cap, C, gc), C=C, group_cols=gc, max_iter=cap, api='groups', rhs='spread', sequence=True))
+    return t
+
+
+SEEDS = {'stack-24x1-masks-f64': 1, 'stack-24x10-plain-f64': 2, 'stack-24x3-masks-f32': 1, 'stack-2x3-masks-f32': 1,
+         'stack-32x1-masks-f32': 3, 'stack-32x1-masks-f64': 2, 'stack-32x1-plain-f32': 1, 'stack-32x3-plain-f64': 2,
+         'stack-7x10-masks-f64': 1}
+
+
+def seed_of(case):
+    return SEEDS.get(case['id'], 0)
+
+
+def build(case, seed=None):
+    """(cached; nobody writes into what it returns)  -> dict(A, B, masks, x0, scale, rows, vals): A as an fp64 CSR matrix whose entries are numbers of the case's format; B the
+    right-hand side the SOLVER gets (with x0: the residual b - A x0, as DeviceGraph.cg asks), zero on the Dirichlet rows."""
+    return _build(case['id'], seed_of(case) if seed is None else seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _build(case_id, seed):
+    case = BY_ID[case_id]
+    dtype = cg_ref.DTYPES[case['dt']]
+    n, C, gc = case['n'], case['C'], case['group_cols']
+    ng = C // gc
+    rng = np.random.default_rng([seed, n, C])
+    if case['op'] == 'banded':
+        A = cg_ref.banded(n)
+    else:
+        # (a 'sequence' case shares its operator with the others of the sequence: one DeviceGraph)
+        A = cg_ref.laplacian_plus(n, 12345 if case.get('sequence') else seed, case['tau'])
+    A = cg_ref.in_format(A, dtype)
+    if case['rhs'] == 'eig':
+        B = np.ones((n, 1)) * np.arange(1, C + 1)
+    else:
+        B = rng.normal(size=(n, C))
+    if case['rhs'] == 'spread':             # the systems stop several iterations apart
+        B = B * np.repeat(np.exp(3 * rng.normal(size=ng)), gc)
+    for z in case['zero_cols']:
+        B[:, z] = 0
+    out = dict(A=A, masks=None, x0=None, scale=None, rows=None, vals=None)
+    if case['masks']:
+        out['masks'] = [np.sort(rng.choice(n, size=int(rng.integers(0, n // 3 + 1)), replace=False)).astype(np.int32) for _ in range(ng)]
+        for g, m in enumerate(out['masks']):
+            B[m, g * gc:(g + 1) * gc] = 0
+    if case['rhs'] == 'rows':               # about 5 % of the rows nonzero
+        keep = rng.random(n) < 0.05
+        keep[rng.integers(0, n)] = True
+        B[~keep] = 0
+    B = B.astype(dtype)
+    if case['x0']:
+        x0 = rng.normal(size=(n, C)).astype(dtype)
+        out['x0'] = x0
+        out['b'] = B                        # the system's right-hand side; the solver is given the residual
+        B = (B - (A @ x0.astype(np.float64)).astype(dtype)).astype(dtype)
+    if case['rhs'] == 'rows':
+        out['rows'] = np.flatnonzero(np.any(B != 0, axis=1)).astype(np.int32)
+        out['vals'] = np.ascontiguousarray(B[out['rows']])
+    if case['out_scale']:
+        out['scale'] = rng.uniform(0.5, 2.0, size=n)
+    out['B'] = np.ascontiguousarray(B)
+    return out
+
+
+class Ref:
+    """x, iteration counts and residual histories per system: `ld` in long double, `own` in the case's format"""
+    pass
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case_id, seed=None):
+    case = BY_ID[case_id]
+    s = build(case, seed)
+    gc = case['group_cols']
+    ref = Ref()
+    for name, dt in (('ld', np.longdouble), ('own', cg_ref.DTYPES[case['dt']])):
+        # with x0 the solver's B is r0 = b - A x0 rounded to the case's format: every format starts from THAT residual, as the device does
+        op = cg_ref.Operator(s['A'], dt)
+        X = np.empty(s['B'].shape, dtype=dt)
+        its, hists = [], []
+        for g in range(case['C'] // gc):
+            cols = slice(g * gc, (g + 1) * gc)
+            hold = s['masks'][g].astype(np.int64) if s['masks'] is not None and len(s['masks'][g]) else None
+            x, it, hist = _solve_from_residual(op, s['B'][:, cols], None if s['x0'] is None else s['x0'][:, cols], case['tol'], case['max_iter'], dt, hold)
+            X[:, cols] = x
+            its.append(it)
+            hists.append(hist)
+        if s['scale'] is not None:
+            X = X * s['scale'][:, None].astype(dt)
+        setattr(ref, name, (X, its, hists))
+    return ref
+
+
+def _solve_from_residual(op, r0, x0, tol, max_iter, dt, hold):
+    return cg_ref.conjgrad(op, r0, x0, tol, max_iter, dt, hold, r0=x0 is not None)
+
+
+def margin(hists, tol):
+    """the smallest relative distance from tol of any residual norm of any system (NaN norms decide nothing: a breakdown stops)"""
+    m = np.inf
+    for h in hists:
+        for e in h:
+            e = float(e)
+            if e == e:
+                m = min(m, abs(e - tol) / tol)
+    return m
+
+
+def d_ref(ref, eps):
+    """max |x_own - x_ld| / max(1, max |x_ld|) over the finite entries, and the largest |err_own - err_ld| of any iteration"""
+    xl, xo = ref.ld[0], ref.own[0]
+    ok = np.isfinite(xl)
+    scale = max(1.0, float(np.max(np.abs(xl[ok])))) if ok.any() else 1.0
+    dx = float(np.max(np.abs(xo[ok].astype(np.longdouble) - xl[ok]))) / scale if ok.any() else 0.0
+    de = 0.0
+    for ho, hl in zip(ref.own[2], ref.ld[2]):
+        for a, b in zip(ho, hl):
+            if float(b) == float(b):
+                de = max(de, abs(float(a) - float(b)))
+    return dx, de, scale
+
+
+CASES = _table()
+BY_ID = {c['id']: c for c in CASES}
+assert len(BY_ID) == len(CASES)
+
+
+def pick_seeds():
+    out = {}
+    for c in CASES:
+        for seed in range(200):
+            ref = reference(c['id'], seed)
+            reference.cache_clear()
+            _build.cache_clear()
+            if margin(ref.ld[2], c['tol']) >= MIN_MARGIN and margin(ref.own[2], c['tol']) >= MIN_MARGIN and ref.ld[1] == ref.own[1]:
+                break
+        else:
+            raise SystemExit('no seed for %s' % c['id'])
+        if seed:
+            out[c['id']] = seed
+    return out
+
+
+if __name__ == '__main__':
+    import pprint
+    pprint.pprint(pick_seeds(), width=150, compact=True)
