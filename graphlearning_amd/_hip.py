@@ -156,6 +156,7 @@ _SIGNATURES = {
     'glx_sssp': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp, _i64p, _f64p, C.c_int],
     'glx_lip_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_double,
                         _vp, _vp, _vp, _vp, C.c_int, C.c_int],
+    'glx_slp_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1127,6 +1128,30 @@ def lip_iterate(n, nbr, row, W, ind, val, weighted, alpha, beta, T, tol, device=
                                  _dev(device)),
           'glx_lip_iterate')
     return u, iters, (int(plan[0]), int(plan[1]), int(plan[2])), errs
+
+
+def slp_iterate(row_ptr, col, W, lam, gamma, ind, val, T, device=None, want_history=False):
+    """T iterations of sparse label propagation on the GPU (glx_slp_iterate, csrc/slp.hip; the contract is DESIGN.md 4.9): W as
+    canonical CSR arrays (row_ptr, col, W), lam per entry, gamma per vertex, the labelled vertices `ind` and the rows `val` (m, C) they are
+    set to.  Returns (u (n, C) float64, the iterates (T, n, C) or None, plan = (launches per iteration, launches enqueued, column tile))."""
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+    ind = np.ascontiguousarray(ind, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    n, T = len(row_ptr) - 1, int(T)
+    if (row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or W.shape != col.shape or lam.shape != col.shape or gamma.shape != (n,) or ind.ndim != 1
+            or val.ndim != 2 or val.shape[0] != len(ind) or val.shape[1] < 1 or T < 0):
+        raise GlxError('slp_iterate: inconsistent array shapes or sizes')
+    Cc = int(val.shape[1])
+    u = np.empty((n, Cc), dtype=np.float64)
+    hist = np.empty((T, n, Cc), dtype=np.float64) if want_history else None
+    plan = (C.c_int64 * 3)(0, 0, 0)
+    check(load().glx_slp_iterate(n, len(col), _ptr(row_ptr), _ptr(col), _ptr(W), _ptr(lam), _ptr(gamma), Cc, len(ind), _ptr(ind), _ptr(val),
+                                 T, _ptr(u), _ptr(hist) if (want_history and T > 0) else None, plan, _dev(device)), 'glx_slp_iterate')
+    return u, hist, (int(plan[0]), int(plan[1]), int(plan[2]))
 
 
 def host_row_sums(W):

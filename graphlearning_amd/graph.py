@@ -136,6 +136,39 @@ class graph:
         self.J = np.ascontiguousarray(self.J, dtype=np.int32)
         self.V = np.ascontiguousarray(self.V, dtype=np.float64)
 
+    def _entries(self):
+        if getattr(self, 'I', None) is None:
+            self.__ccode_init__()
+        return self.I, self.J, self.V
+
+    def adjacency(self):
+        """The 0/1 pattern of the weight matrix as a float CSR matrix: A_ij = 1 where w_ij is stored and nonzero (reference
+        graph.py:274-290).  Host scipy, on the arrays of __ccode_init__."""
+        I, J, V = self._entries()
+        n = self.num_nodes
+        return sparse.coo_matrix((np.ones(len(V)), (I, J)), shape=(n, n)).tocsr()
+
+    def gradient(self, u, weighted=False, p=0.0):
+        """Graph gradient of the vertex function u: the sparse matrix with (u_j - u_i) on every entry (i, j) of the weight matrix,
+        times w_ij^p when weighted (reference graph.py:292-332: p != 0 implies weighted, weighted with p == 0 means p = 1).  Host scipy."""
+        I, J, V = self._entries()
+        n = self.num_nodes
+        if p != 0.0:
+            weighted = True
+        if weighted == True and p == 0.0:
+            p = 1.0
+        diff = u[J] - u[I]
+        vals = (V ** p) * diff if weighted else diff
+        return sparse.coo_matrix((vals, (I, J)), shape=(n, n)).tocsr()
+
+    def divergence(self, V, weighted=True):
+        """Graph divergence of the edge field V (a sparse matrix): half the row sums of V - V^T, entry by entry times the weight
+        matrix when weighted (reference graph.py:334-365).  Host scipy."""
+        V = V - V.transpose()
+        if weighted:
+            V = V.multiply(self.weight_matrix)
+        return V * np.ones(self.num_nodes) / 2
+
     def plaplace(self, bdy_set, bdy_val, p, tol=1e-1, max_num_it=1e6, prog=False, fast=True, device=None):
         """Game-theoretic p-Laplace equation with Dirichlet data (reference graph.py:1177-1278).
         `fast=False` -- the Jacobi iteration of upper / lower barriers, lp_iterate_main of the

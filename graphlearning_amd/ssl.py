@@ -1262,6 +1262,80 @@ class amle(ssl):
         return u
 
 
+SLP_HISTORY_BYTES = 1 << 30       # sparse_label_propagation with all_labels: the iterates (T, n, k) the device call hands back, at most
+
+
+class sparse_label_propagation(ssl):
+    def __init__(self, W=None, class_priors=None, T=100):
+        """Sparse label propagation (reference ssl.py:1429-1508; Jung, Hero, Mara and Jahromi, arXiv:1612.01414): T primal-dual sweeps
+        for the total-variation problem, a field on the edges beside the labels on the vertices, all classes as the columns of one
+        device call (_hip.slp_iterate; the contract is DESIGN.md 4.9) with the reference's `prob` bit for bit.  Not one-vs-rest.
+        With `all_labels` the reference's lines `i,Accuracy = ..` are printed after the solve, from the iterates the call returns.
+        Refused with ValueError (the reference answers NaN or an indexing error there): a vertex without a stored entry, a weight
+        that is negative, zero after duplicates are summed, NaN or infinite, a training index out of range, labels that are not
+        exactly 0 .. k-1, index and label arrays of different lengths, an iterate history above 1 GiB."""
+        super().__init__(W, class_priors)
+        self.T = T
+        self.accuracy_filename = '_sparse_label_propagation'
+        self.name = 'Sparse LP'
+
+    def _operands(self):
+        """The canonical CSR arrays of the weight matrix with lam per entry and gamma per vertex (host numpy: the reference's own
+        element-wise calls), rebuilt in every fit as the reference does."""
+        W = sparse.csr_matrix(self.graph.weight_matrix, dtype=np.float64, copy=True)
+        W.sum_duplicates()
+        bad = ~(np.isfinite(W.data) & (W.data >= 0))
+        if bad.any():
+            raise ValueError('sparse_label_propagation: weight %r is negative, NaN or infinite' % (W.data[bad][0],))
+        W.eliminate_zeros()
+        W.sort_indices()
+        if not np.all(W.data > 0):
+            raise ValueError('sparse_label_propagation: a weight is zero after eliminate_zeros')
+        empty = np.where(np.diff(W.indptr) == 0)[0]
+        if len(empty):
+            raise ValueError('sparse_label_propagation: vertex %d has no stored entry (its degree is zero; the reference returns NaN '
+                             'there)' % int(empty[0]))
+        w = np.ascontiguousarray(W.data)
+        lam = np.expm1(-np.log1p(2 * w - (1 - 1e-10))) + 1.0
+        gamma = self.graph.degree_vector() ** -1
+        if not (np.all(np.isfinite(lam)) and np.all(np.isfinite(gamma))):
+            raise ValueError('sparse_label_propagation: a step size (lam or 1/degree) is not finite')
+        return W.indptr.astype(np.int64), W.indices.astype(np.int32), w, lam, gamma
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        n = self.graph.num_nodes
+        T = max(int(self.T), 0)
+        train_ind = np.asarray(train_ind).ravel()
+        train_labels = np.asarray(train_labels).ravel()
+        if len(train_ind) != len(train_labels):
+            raise ValueError('sparse_label_propagation: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
+        if len(train_ind) == 0:
+            raise ValueError('sparse_label_propagation: no training vertex')
+        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
+            raise ValueError('sparse_label_propagation: train_ind out of range (or not an integer array)')
+        classes = np.unique(train_labels)
+        k = len(classes)
+        if not np.array_equal(classes, np.arange(k)):
+            raise ValueError('sparse_label_propagation: the labels are not exactly 0 .. %d' % (k - 1))
+        want_hist = all_labels is not None and T > 0
+        if want_hist and T * n * k * 8 > SLP_HISTORY_BYTES:
+            raise ValueError('sparse_label_propagation: the iterates of an all_labels fit take %d bytes (T=%d x n=%d x k=%d doubles), '
+                             'above the limit of %d' % (T * n * k * 8, T, n, k, SLP_HISTORY_BYTES))
+        row_ptr, col, w, lam, gamma = self._operands()
+        val = (train_labels.astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
+        u, hist, plan = _hip.slp_iterate(row_ptr, col, w, lam, gamma, train_ind.astype(np.int32), val, T, device=self.device,
+                                         want_history=want_hist)
+        self.num_iter = T
+        self.slp_plan = plan
+        if want_hist:                     # the reference's lines (ssl.py:1502-1506), one per iteration, on each iterate
+            for i in range(T):
+                self.prob = hist[i]
+                acc = ssl_accuracy(self.predict(), all_labels, train_ind)
+                sys.stdout.write('%d,Accuracy = %.2f\n' % (i, acc))
+            sys.stdout.flush()
+        return u
+
+
 def ssl_accuracy(pred_labels, true_labels, train_ind):
     """Accuracy in percent over nodes outside train_ind with a true label >= 0
     (reference ssl.py:1795-1834: `100*np.mean(pred[mask] == true[mask])` over the masked arrays).  The same number from

@@ -215,6 +215,22 @@ int glx_lip_iterate(int64_t n, int64_t M, const int32_t* nbr, const int32_t* row
                     const double* val, int weighted, double alpha, double beta, int64_t T, double tol, double* u, int64_t* iters_out,
                     int64_t* plan_out, double* err_hist, int small_level, int device);
 
+/* ---- sparse label propagation: ssl.sparse_label_propagation (csrc/slp.hip, csrc/slp_plan.h) ----------------------------------------
+ * The primal-dual total-variation sweeps of the reference's ssl.sparse_label_propagation (ssl.py:1429-1508) bit for bit; the contract,
+ * every operation rounded on its own, is DESIGN.md 4.9.  W arrives as canonical CSR: n rows, M entries, row_ptr (n + 1), col ascending
+ * inside a row without duplicates, W finite and > 0, no empty row.  lam (M) per entry and gamma (n) per vertex are the caller's (the
+ * host's expm1 / log1p and degree ** -1).  C >= 1 class columns share the m labelled vertices ind (a vertex listed twice takes its
+ * last row); val (m, C) row-major are the rows they are set to in every iteration.  u and the edge state start at zero; T iterations
+ * of two launches each (vertex phase, edge phase), full chunks replayed from a captured launch sequence; more than 16 columns run as
+ * tiles of at most 16, one after another, and the result does not depend on the tiling.
+ * u (n, C) row-major: the result (zeros for T = 0, also on the labelled vertices).  u_hist (T, n, C) or NULL: u after every iteration.
+ * plan_out[3] (or NULL): launches per iteration, sweep launches enqueued in all, columns of the widest tile.  All pointers are host
+ * pointers.  GLX_EINVAL: a null argument, C < 1, rows that are not canonical, an index out of range, a weight that is not finite and
+ * > 0, a non-finite lam or gamma, an empty row. */
+int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* W, const double* lam,
+                    const double* gamma, int C, int64_t m, const int32_t* ind, const double* val, int64_t T, double* u, double* u_hist,
+                    int64_t* plan_out, int device);
+
 #ifdef __cplusplus
 }
 #endif
