@@ -157,6 +157,8 @@ _SIGNATURES = {
     'glx_lip_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_double,
                         _vp, _vp, _vp, _vp, C.c_int, C.c_int],
     'glx_slp_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
+    'glx_lp_iterate_batch': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_double, C.c_int64, C.c_double, _vp, _vp, _vp,
+                             C.c_int],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1061,6 +1063,28 @@ def lp_iterate(uu, ul, nbr, row, W, ind, val, p, T, tol, device=None):
     check(load().glx_lp_iterate(_ptr(uu), _ptr(ul), _ptr(nbr), _ptr(row), _ptr(W), _ptr(ind), _ptr(val), float(p), int(T), float(tol),
                                 len(uu), len(W), len(ind), C.byref(it), _dev(device)), 'glx_lp_iterate')
     return it.value
+
+
+def lp_iterate_batch(n, nbr, row, W, ind, val, p, T, tol, device=None):
+    """B problems of `lp_iterate` that share the boundary vertices `ind`, one per column of `val` (m, B), in one device call
+    (glx_lp_iterate_batch, csrc/plaplace.hip): column b starts from uu = max(val[:, b]), ul = min(val[:, b]) off the boundary.  Returns
+    (uu (n, B), ul (n, B), stopping iteration per column (B,) int64); every column equals its own `lp_iterate` call bit for bit."""
+    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+    row = np.ascontiguousarray(row, dtype=np.int32)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    ind = np.ascontiguousarray(ind, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    if val.ndim != 2 or val.shape[0] != len(ind) or nbr.ndim != 1 or len(nbr) != len(row) or len(nbr) != len(W) or ind.ndim != 1:
+        raise GlxError('lp_iterate_batch: inconsistent array shapes')
+    n, B, T = int(n), int(val.shape[1]), int(T)
+    if n < 1 or B < 1 or T < 0:
+        raise GlxError('lp_iterate_batch: bad sizes (n=%d B=%d T=%d)' % (n, B, T))
+    uu = np.empty((n, B), dtype=np.float64)
+    ul = np.empty((n, B), dtype=np.float64)
+    iters = np.zeros(B, dtype=np.int64)
+    check(load().glx_lp_iterate_batch(n, len(nbr), _ptr(nbr), _ptr(row), _ptr(W), B, len(ind), _ptr(ind), _ptr(val), float(p), T, float(tol),
+                                      _ptr(uu), _ptr(ul), _ptr(iters), _dev(device)), 'glx_lp_iterate_batch')
+    return uu, ul, iters
 
 
 GLX_SSSP_PLAIN, GLX_SSSP_HOPF_LAX = 0, 1

@@ -206,6 +206,33 @@ class graph:
             raise ValueError('graph.amle: the weight matrix has a negative or NaN entry')
         return np.bincount(self.I, minlength=self.num_nodes) > 0
 
+    def _lip_checked(self, what, bdy_set, vals, max_num_it):
+        """The arguments of a batched in-order sweep (_hip.lip_iterate), checked: (bdy_set int64, vals (m, B) float64, T).  ValueError,
+        before any device call: values whose shape does not match the boundary set, an index out of range, a non-finite value, more
+        than 2^24 sweeps, a negative or NaN weight, a vertex off the boundary without a stored entry."""
+        from . import utils
+        n = self.num_nodes
+        bdy_set, _ = utils._boundary_handling(bdy_set, 0)
+        bdy_set = np.ascontiguousarray(bdy_set, dtype=np.int64).ravel()
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if vals.ndim != 2 or vals.shape[0] != len(bdy_set) or vals.shape[1] < 1:
+            raise ValueError('%s: boundary values of shape %s for %d boundary vertices' % (what, vals.shape, len(bdy_set)))
+        if len(bdy_set) and (bdy_set.min() < 0 or bdy_set.max() >= n):
+            raise ValueError('%s: boundary index out of range' % what)
+        if not np.all(np.isfinite(vals)):
+            raise ValueError('%s: bdy_val has a non-finite entry' % what)
+        T = int(float(max_num_it))
+        if T > (1 << 24):
+            raise ValueError('%s: max_num_it=%r above the supported 2^24 sweeps' % (what, max_num_it))
+        T = max(T, 0)                    # `for(it=0;it<T;it++)`: a negative T sweeps nothing
+        has_entry = self._amle_entries()
+        free = ~has_entry
+        free[bdy_set] = False
+        if free.any():
+            raise ValueError('%s: vertex %d is not on the boundary and has no stored entry (the reference reads another '
+                             'vertex\'s entry there)' % (what, int(np.where(free)[0][0])))
+        return bdy_set, vals, T
+
     def _amle_batch(self, bdy_set, vals, tol=1e-5, max_num_it=1000, weighted=True, prog=False, device=None, small_level=-1):
         """B AMLE problems that share the boundary vertices `bdy_set`, one per column of `vals` (m, B), in one device call
         (glx_lip_iterate): returns u (n, B) float64; every column equals its single `amle` call bit for bit, and stops on its own.
@@ -213,30 +240,12 @@ class graph:
         With `prog` the reference's progress lines are printed AFTER the solve, from the errors the host read while it ran, one
         column after another (the order of the reference's class-by-class calls).  small_level: plan override for measurements
         (_hip.lip_iterate); the result does not depend on it."""
-        from . import _hip, utils
+        from . import _hip
         n = self.num_nodes
-        bdy_set, _ = utils._boundary_handling(bdy_set, 0)
-        bdy_set = np.ascontiguousarray(bdy_set, dtype=np.int64).ravel()
-        vals = np.ascontiguousarray(vals, dtype=np.float64)
-        if vals.ndim != 2 or vals.shape[0] != len(bdy_set) or vals.shape[1] < 1:
-            raise ValueError('graph.amle: boundary values of shape %s for %d boundary vertices' % (vals.shape, len(bdy_set)))
-        if len(bdy_set) and (bdy_set.min() < 0 or bdy_set.max() >= n):
-            raise ValueError('graph.amle: boundary index out of range')
-        if not np.all(np.isfinite(vals)):
-            raise ValueError('graph.amle: bdy_val has a non-finite entry')
         tol = float(tol)
+        bdy_set, vals, T = self._lip_checked('graph.amle', bdy_set, vals, max_num_it)
         if not np.isfinite(tol):
             raise ValueError('graph.amle: tol is not finite')
-        T = int(float(max_num_it))
-        if T > (1 << 24):
-            raise ValueError('graph.amle: max_num_it=%r above the supported 2^24 sweeps' % (max_num_it,))
-        T = max(T, 0)                    # `for(it=0;it<T;it++)`: a negative T sweeps nothing
-        has_entry = self._amle_entries()
-        free = ~has_entry
-        free[bdy_set] = False
-        if free.any():
-            raise ValueError('graph.amle: vertex %d is not on the boundary and has no stored entry (the reference reads another '
-                             'vertex\'s entry there)' % int(np.where(free)[0][0]))
         u, iters, plan, errs = _hip.lip_iterate(n, self.J, self.I, self.V, bdy_set.astype(np.int32), vals, weighted, 0.0, 1.0, T, tol,
                                                 device=device, want_errors=bool(prog), small_level=small_level)
         self.amle_iters = iters
@@ -248,6 +257,46 @@ class graph:
                     sys.stdout.write('Iter=%d, err=%.15f\n' % (it, errs[it, b]))
             sys.stdout.flush()
         return u
+
+    def _plaplace_batch(self, bdy_set, vals, p, tol=1e-1, max_num_it=1e6, fast=True, device=None):
+        """B p-Laplace problems (reference graph.py:1177-1278) that share the boundary vertices `bdy_set`, one per column of `vals`
+        (m, B), in one device call: returns u (n, B) float64 and sets plaplace_iters (B,).  Every column stops on its own.
+        fast=True: the reference's in-order Gauss-Seidel sweeps lip_iterate_main with alpha = 1/(p-1), beta = 1-alpha on the 0/1
+        pattern, from zero, tol overridden to 1e-6 (graph.py:1259-1261), level by level through _hip.lip_iterate like graph.amle, with
+        graph.amle's refusals; also sets plaplace_levels and plaplace_plan.  fast=False: the Jacobi iteration of upper and lower
+        barriers through _hip.lp_iterate_batch, every column bit for bit its `plaplace(fast=False)` call; returns (uu + ul) / 2.
+        Refused there with ValueError: values whose shape does not match the boundary set, an index out of range, more than 2^24
+        iterations; a vertex without entries gives NaN as in the single call."""
+        from . import _hip, utils
+        n = self.num_nodes
+        if fast:
+            alpha = 1 / (p - 1)
+            beta = 1 - alpha
+            tol = 1e-6
+            bdy_set, vals, T = self._lip_checked('graph.plaplace', bdy_set, vals, max_num_it)
+            u, iters, plan, _ = _hip.lip_iterate(n, self.J, self.I, self.V, bdy_set.astype(np.int32), vals, False, alpha, beta, T, tol,
+                                                 device=device)
+            self.plaplace_iters = iters
+            self.plaplace_levels = plan[0]
+            self.plaplace_plan = plan
+            return u
+        bdy_set, _ = utils._boundary_handling(bdy_set, 0)
+        bdy_set = np.ascontiguousarray(bdy_set, dtype=np.int64).ravel()
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if vals.ndim != 2 or vals.shape[0] != len(bdy_set) or vals.shape[1] < 1:
+            raise ValueError('graph.plaplace: boundary values of shape %s for %d boundary vertices' % (vals.shape, len(bdy_set)))
+        if len(bdy_set) == 0:
+            raise ValueError('graph.plaplace: no boundary vertex (the barriers start from the largest and smallest boundary value)')
+        if bdy_set.min() < 0 or bdy_set.max() >= n:
+            raise ValueError('graph.plaplace: boundary index out of range')
+        T = int(float(max_num_it))
+        if T > (1 << 24):
+            raise ValueError('graph.plaplace: max_num_it=%r above the supported 2^24 iterations' % (max_num_it,))
+        T = max(T, 0)
+        I, J, V = self._entries()
+        uu, ul, iters = _hip.lp_iterate_batch(n, J, I, V, bdy_set.astype(np.int32), vals, p, T, float(tol), device=device)
+        self.plaplace_iters = iters
+        return (uu + ul) / 2
 
     def amle(self, bdy_set, bdy_val, tol=1e-5, max_num_it=1000, weighted=True, prog=False, device=None):
         """Absolutely minimal Lipschitz extension of the boundary values: the solution of the graph infinity-Laplace equation

@@ -1262,6 +1262,40 @@ class amle(ssl):
         return u
 
 
+class plaplace(ssl):
+    def __init__(self, W=None, class_priors=None, p=10, max_num_it=1e6, tol=1e-1, fast=True):
+        """Semi-supervised learning by the game-theoretic p-Laplace equation (reference ssl.py:1681-1727; Flores Rios, Calder and
+        Lerman, arXiv:1901.05031): one-vs-rest, class l's score is graph.plaplace of the 0/1 indicator of its labelled vertices.
+        `fast=True` (the reference's default) runs the in-order Gauss-Seidel sweeps with constant weights on the infinity-Laplace
+        term, `fast=False` the Jacobi iteration of upper and lower barriers.  All classes are solved as the columns of one device call
+        (graph._plaplace_batch); every column stops on its own, as the reference's class-by-class calls do.  With `fast` the
+        reference sets tol = 1e-5 here and graph.plaplace then solves to 1e-6 whatever it is given: both are kept."""
+        super().__init__(W, class_priors)
+        self.p = p
+        self.max_num_it = max_num_it
+        self.tol = tol
+        self.onevsrest = True
+        self.fast = fast
+        if fast:
+            self.tol = 1e-5
+        self.accuracy_filename = '_plaplace_p%.2f' % self.p
+        self.name = 'p-Laplace (p=%.2f)' % self.p
+
+    def _solve(self, train_ind, vals):
+        u = self.graph._plaplace_batch(train_ind, vals, self.p, tol=self.tol, max_num_it=self.max_num_it, fast=self.fast, device=self.device)
+        self.num_iter = [int(i) for i in self.graph.plaplace_iters]
+        return u
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        # one class: the same batch call with one column (graph.plaplace itself stays refused for fast=True)
+        vals = np.asarray(train_labels).astype(np.float64).reshape(-1, 1)
+        return np.ascontiguousarray(self._solve(train_ind, vals)[:, 0])
+
+    def _fit_onevsrest(self, train_ind, train_labels, unique_labels):
+        vals = (train_labels[:, None] == unique_labels[None, :]).astype(np.float64)      # `train_labels == l` cast like the reference's bdy_val
+        return self._solve(train_ind, vals)
+
+
 SLP_HISTORY_BYTES = 1 << 30       # sparse_label_propagation with all_labels: the iterates (T, n, k) the device call hands back, at most
 
 

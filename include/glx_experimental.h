@@ -231,6 +231,20 @@ int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t*
                     const double* gamma, int C, int64_t m, const int32_t* ind, const double* val, int64_t T, double* u, double* u_hist,
                     int64_t* plan_out, int device);
 
+/* ---- p-Laplace Jacobi iteration, all columns in one call: ssl.plaplace(fast=False) (csrc/plaplace.hip, csrc/lp_plan.h) -------------
+ * B problems of glx_lp_iterate (glx.h) on one graph that share the m boundary vertices ind (a vertex listed twice takes its last
+ * row); val (m, B) row-major are their values, one problem per column.  Column b starts from uu = max(val[:, b]), ul = min(val[:, b])
+ * off the boundary (NaN if the column holds one; -inf / +inf for m = 0) and val on it.  nbr / row / W (M): the stored entries sorted by
+ * vertex, as glx_lp_iterate takes them.  Every column equals, bit for bit, what glx_lp_iterate returns for that column alone: uu, ul
+ * (the content of the first of the two iterate buffers: U_S for a stop at an even iteration S, U_{S+1} at an odd one) and the
+ * stopping iteration.  A column stops on its own at the first `it` with err < tol && it > 10 and is written by no later iteration.
+ * uu, ul (n, B) row-major: the results.  iters_out[B] (or NULL): the stopping iteration per column (T if never).  1 <= B <= 256,
+ * T <= 2^24, n * B <= 2^31 (GLX_EUNSUPPORTED beyond).  All pointers are host pointers.  GLX_EINVAL: a null argument, bad sizes, an
+ * index out of range. */
+int glx_lp_iterate_batch(int64_t n, int64_t M, const int32_t* nbr, const int32_t* row, const double* W, int B, int64_t m,
+                         const int32_t* ind, const double* val, double p, int64_t T, double tol, double* uu, double* ul,
+                         int64_t* iters_out, int device);
+
 #ifdef __cplusplus
 }
 #endif
