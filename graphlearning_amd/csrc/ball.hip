@@ -408,23 +408,6 @@ extern "C" int glx_ball_result_nnz(const glx_ball_result* res, int64_t* nnz_out)
 }
 
 namespace {
-struct BallBufs {
-  void* p[16] = {};
-  int np = 0;
-  glx_work* work = nullptr;
-  hipStream_t stream = nullptr;
-  int alloc(void** out, size_t bytes) {
-    const int rc = glx_pool_alloc(out, std::max<size_t>((bytes + 7) & ~(size_t)7, 8));
-    if (!rc) p[np++] = *out;
-    return rc;
-  }
-  ~BallBufs() {
-    if (stream) hipStreamSynchronize(stream);   // pooled blocks are reused at once
-    for (int i = 0; i < np; ++i) glx_pool_free(p[i]);
-    glx_work_release(work);
-  }
-};
-
 template <bool FILL>
 int launch_pairs(int d, unsigned grid, hipStream_t st, const double* Xs, const int* orig, const int* scell, const long long* cell_start,
                  int64_t n, const BallGrid& G, double eps2, int* cnt, const long long* off, int* col, unsigned long long* tested) {
@@ -439,13 +422,9 @@ int launch_pairs(int d, unsigned grid, hipStream_t st, const double* Xs, const i
 }
 
 int ball_search_impl(const double* X, int64_t n, int d, double epsilon, const double* F, int mf, int device, glx_ball_result* res) {
-  GLX_HIP(hipSetDevice(device));
-  BallBufs b;
-  {
-    const int rcw = glx_work_acquire(device, &b.work);
-    if (rcw) return rcw;
-  }
-  hipStream_t st = b.stream = b.work->stream;
+  GlxCall call;
+  GLX_UP(call.begin(device));
+  hipStream_t st = call.stream();
   for (int i = 0; i < BS_COUNT; ++i) g_ball_stats[i] = 0.0;
   // the bounding box, on the host's threads, BEFORE anything travels: the plan and the finiteness refusal need it, and a checked
   // upload (glx_upload) ends in a stream synchronisation of its own, so there is nothing to overlap it with
@@ -494,18 +473,18 @@ int ball_search_impl(const double* X, int64_t n, int d, double epsilon, const do
   long long* cell_start;
   double* Xs;
   unsigned long long* counters;    // [0] pairs tested, [1] (int) hub rows
-  GLX_POOL(b.alloc((void**)&cid, (size_t)n * 4));
-  GLX_POOL(b.alloc((void**)&cell_cnt, (size_t)plan.ncells * 4));
-  GLX_POOL(b.alloc((void**)&cell_start, (size_t)(plan.ncells + 1) * 8));
-  GLX_POOL(b.alloc((void**)&orig, (size_t)n * 4));
-  GLX_POOL(b.alloc((void**)&scell, (size_t)n * 4));
-  GLX_POOL(b.alloc((void**)&Xs, (size_t)n * d * 8));
-  GLX_POOL(b.alloc((void**)&cnt, (size_t)n * 4));
-  GLX_POOL(b.alloc((void**)&hubs, (size_t)n * 4));
-  GLX_POOL(b.alloc((void**)&counters, 16));
+  GLX_POOL(call.alloc(&cid, (size_t)n));
+  GLX_POOL(call.alloc(&cell_cnt, (size_t)plan.ncells));
+  GLX_POOL(call.alloc(&cell_start, (size_t)(plan.ncells + 1)));
+  GLX_POOL(call.alloc(&orig, (size_t)n));
+  GLX_POOL(call.alloc(&scell, (size_t)n));
+  GLX_POOL(call.alloc(&Xs, (size_t)n * d));
+  GLX_POOL(call.alloc(&cnt, (size_t)n));
+  GLX_POOL(call.alloc(&hubs, (size_t)n));
+  GLX_POOL(call.alloc(&counters, 2));
   GLX_UP(glx_zero_async(cell_cnt, ((size_t)plan.ncells * 4 + 7) & ~(size_t)7, st));
   GLX_UP(glx_zero_async(counters, 16, st));
-  hipEvent_t* ev = b.work->ev;
+  hipEvent_t* ev = call.work()->ev;
   const unsigned gn = (unsigned)((n + 255) / 256);
   GLX_HIP(hipEventRecord(ev[0], st));
   hipLaunchKernelGGL(ball_cellid_kernel, dim3(gn), dim3(256), 0, st, (const double*)res->X, n, d, G, cid, cell_cnt);
@@ -524,7 +503,7 @@ int ball_search_impl(const double* X, int64_t n, int d, double epsilon, const do
   GLX_HIP(hipEventRecord(ev[2], st));
   // the total, the hub rows and the tested pairs land in the work set's page-locked staging area
   unsigned long long* stage = nullptr;
-  GLX_POOL(glx_work_stage(b.work, 64, (void**)&stage));
+  GLX_POOL(call.stage(&stage, 8));
   // (24 bytes into page-locked memory: far below the size from which glx_download stages and checks a transfer, so a plain copy)
   GLX_HIP(hipMemcpyAsync(stage, counters, 16, hipMemcpyDeviceToHost, st));
   GLX_HIP(hipMemcpyAsync(stage + 2, res->off + n, 8, hipMemcpyDeviceToHost, st));
@@ -604,23 +583,19 @@ extern "C" int glx_ball_result_to_csr(const glx_ball_result* res, int kernel, do
     for (int64_t i = 0; i <= n; ++i) rowptr[i] = 0;
     return GLX_OK;
   }
-  GLX_HIP(hipSetDevice(res->device));
-  BallBufs b;
-  {
-    const int rcw = glx_work_acquire(res->device, &b.work);
-    if (rcw) return rcw;
-  }
-  hipStream_t st = b.stream = b.work->stream;
+  GlxCall call;
+  GLX_UP(call.begin(res->device));
+  hipStream_t st = call.stream();
   double *dval, *dd = nullptr, *dfd = nullptr;
   int *kept, *rp32;
   long long* off2;
-  GLX_POOL(b.alloc((void**)&dval, (size_t)nnz * 8));
-  if (dists_out) GLX_POOL(b.alloc((void**)&dd, (size_t)nnz * 8));
-  if (fdists_out) GLX_POOL(b.alloc((void**)&dfd, (size_t)nnz * 8));
-  GLX_POOL(b.alloc((void**)&kept, (size_t)n * 4));
-  GLX_POOL(b.alloc((void**)&off2, (size_t)(n + 1) * 8));
-  GLX_POOL(b.alloc((void**)&rp32, (size_t)(n + 1) * 4));
-  hipEvent_t* ev = b.work->ev;
+  GLX_POOL(call.alloc(&dval, (size_t)nnz));
+  if (dists_out) GLX_POOL(call.alloc(&dd, (size_t)nnz));
+  if (fdists_out) GLX_POOL(call.alloc(&dfd, (size_t)nnz));
+  GLX_POOL(call.alloc(&kept, (size_t)n));
+  GLX_POOL(call.alloc(&off2, (size_t)(n + 1)));
+  GLX_POOL(call.alloc(&rp32, (size_t)(n + 1)));
+  hipEvent_t* ev = call.work()->ev;
   const unsigned gr = (unsigned)((n * BALL_ROW_LANES + 255) / 256);
   GLX_HIP(hipEventRecord(ev[0], st));
   hipLaunchKernelGGL(ball_weights_kernel, dim3(gr), dim3(256), 0, st, (const double*)res->X, (const double*)res->F, n, res->d, res->mf,
@@ -631,7 +606,7 @@ extern "C" int glx_ball_result_to_csr(const glx_ball_result* res, int kernel, do
   GLX_HIP(hipGetLastError());
   GLX_HIP(hipEventRecord(ev[1], st));
   unsigned long long* stage = nullptr;
-  GLX_POOL(glx_work_stage(b.work, 64, (void**)&stage));
+  GLX_POOL(call.stage(&stage, 8));
   GLX_HIP(hipMemcpyAsync(stage, off2 + n, 8, hipMemcpyDeviceToHost, st));   // (8 bytes into page-locked memory: a plain copy, as above)
   GLX_HIP(hipStreamSynchronize(st));
   const int64_t nkeep = (int64_t)stage[0];
@@ -648,8 +623,8 @@ extern "C" int glx_ball_result_to_csr(const glx_ball_result* res, int kernel, do
     GLX_CHECK(!dists_out && !fdists_out, GLX_EINVAL, "glx_ball_result_to_csr: distances of a matrix with dropped entries");
     int* col2;
     double* val2;
-    GLX_POOL(b.alloc((void**)&col2, (size_t)nkeep * 4));
-    GLX_POOL(b.alloc((void**)&val2, (size_t)nkeep * 8));
+    GLX_POOL(call.alloc(&col2, (size_t)nkeep));
+    GLX_POOL(call.alloc(&val2, (size_t)nkeep));
     hipLaunchKernelGGL(ball_compact_kernel, dim3(gr), dim3(256), 0, st, n, (const long long*)res->off, (const int*)res->col,
                        (const double*)dval, (const long long*)off2, col2, val2);
     GLX_HIP(hipGetLastError());

@@ -173,6 +173,64 @@ int glx_compare_readback(const void* host, const void* dev, size_t bytes, GlxRea
 void glx_host_parallel(int nt, const std::function<void(int)>& fn);
 #define GLX_UP(call) do { const int rc_up_ = (call); if (rc_up_) return rc_up_; } while (0)
 
+// What one blocking library call holds on the device: a work set (its stream, events and staging area) and the pooled blocks that do
+// not outlive the call.  Blocks a result keeps (a glx_graph's, a glx_ball_result's) stay on glx_pool_alloc directly.  Every member
+// returns a GLX_* code.  The destructor lets go in this order -- pooled blocks and work sets are reused at once, so nothing may still
+// be in flight on them: drain the stream (and the side stream, if side() was asked for), destroy the captured launch sequence, free the
+// blocks, release the work set.  Safe when begin() failed or was never called.
+class GlxCall {
+ public:
+  GlxCall() = default;
+  GlxCall(const GlxCall&) = delete;
+  GlxCall& operator=(const GlxCall&) = delete;
+  ~GlxCall() {
+    if (work_) {
+      hipStreamSynchronize(work_->stream);
+      if (side_used_) hipStreamSynchronize(work_->side);
+    }
+    drop_exec();
+    for (void* p : blocks_) glx_pool_free(p);
+    glx_work_release(work_);
+  }
+  int begin(int device) {
+    GLX_HIP(hipSetDevice(device));
+    return glx_work_acquire(device, &work_);
+  }
+  hipStream_t stream() const { return work_->stream; }
+  hipStream_t side() { side_used_ = true; return work_->side; }
+  glx_work* work() const { return work_; }
+  // a pooled block of `count` elements: rounded up to 8 bytes and at least 8, so a zero count still yields a valid pointer
+  template <class T> int alloc(T** out, size_t count) {
+    const size_t bytes = (count * sizeof(T) + 7) & ~(size_t)7;
+    void* p = nullptr;
+    GLX_UP(glx_pool_alloc(&p, bytes ? bytes : 8));
+    blocks_.push_back(p);
+    *out = (T*)p;
+    return GLX_OK;
+  }
+  // alloc, then the host array goes up in the call's stream (nothing travels at count == 0)
+  template <class T> int put(T** out, const T* host, size_t count, const char* what) {
+    GLX_UP(alloc(out, count));
+    return count ? glx_upload(*out, host, count * sizeof(T), work_->stream, what) : GLX_OK;
+  }
+  // `count` elements of the work set's page-locked staging area
+  template <class T> int stage(T** out, size_t count) { return glx_work_stage(work_, count * sizeof(T), (void**)out); }
+  // a captured launch sequence: the call destroys it, at the latest when it ends
+  hipGraphExec_t exec = nullptr;
+  void drop_exec() {
+    if (exec) hipGraphExecDestroy(exec);
+    exec = nullptr;
+  }
+
+ private:
+  glx_work* work_ = nullptr;
+  bool side_used_ = false;
+  std::vector<void*> blocks_;
+};
+// the (chunk + 1, B) error slots of a new chunk of a chunked iteration (lp_slots_next of lp_plan.h, on the device): slot 0 <- the last
+// slot of the chunk before (prev_len iterations; 0: the first chunk), the others <- 0
+int glx_slots_next_async(unsigned long long* err, int B, int chunk, int prev_len, hipStream_t st);
+
 int glx_graph_plan(glx_graph* g, int G, SellPlan** out, bool relaxed = false);
 int glx_graph_ensure_order(glx_graph* g);
 

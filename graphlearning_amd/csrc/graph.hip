@@ -226,11 +226,9 @@ extern "C" int glx_graph_create_resident(int64_t n_rows, int64_t n_cols, int64_t
   g->h_rowptr.assign(rowptr, rowptr + n_rows + 1);
   g->plans.reserve(8);
   struct Guard { glx_graph* g; ~Guard() { if (g) glx_graph_destroy(g); } } guard{g};
-  glx_work* w = nullptr;
-  int rc = glx_work_acquire(device, &w);
-  if (rc) return rc;
-  struct WorkGuard { glx_work* w; ~WorkGuard() { hipStreamSynchronize(w->stream); glx_work_release(w); } } wguard{w};
-  hipStream_t st = w->stream;
+  GlxCall call;
+  GLX_UP(call.begin(device));
+  hipStream_t st = call.stream();
   GLX_POOL(glx_pool_alloc((void**)&g->d_src_rowptr, (size_t)(n_rows + 1) * 4));
   GLX_POOL(glx_pool_alloc((void**)&g->d_src_col, std::max<size_t>((size_t)nnz * 4, 4)));
   GLX_POOL(glx_pool_alloc((void**)&g->d_src_val, std::max<size_t>((size_t)nnz * 8, 8)));
@@ -241,16 +239,11 @@ extern "C" int glx_graph_create_resident(int64_t n_rows, int64_t n_cols, int64_t
   }
   // column range check (+ the row sums) on the device; results through the work set's page-locked staging area
   char* stage = nullptr;
-  rc = glx_work_stage(w, (size_t)n_rows * 8 + 64, (void**)&stage);
-  if (rc) return rc;
+  GLX_UP(call.stage(&stage, (size_t)n_rows * 8 + 64));
   double* d_sum = nullptr;
   int* d_bad = nullptr;
-  struct Tmp { void *a = nullptr, *b = nullptr; ~Tmp() { glx_pool_free(a); glx_pool_free(b); } } tmp;
-  rc = glx_pool_alloc(&tmp.a, std::max<size_t>((size_t)n_rows * 8, 8));
-  if (!rc) rc = glx_pool_alloc(&tmp.b, 64);
-  if (rc) return rc;
-  d_sum = (double*)tmp.a;
-  d_bad = (int*)tmp.b;
+  GLX_UP(call.alloc(&d_sum, (size_t)n_rows));
+  GLX_UP(call.alloc(&d_bad, 16));
   GLX_HIP(hipMemsetAsync(d_bad, 0, 4, st));
   if (n_rows > 0) {
     hipLaunchKernelGGL(csr_check_rowsum_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, (const int32_t*)g->d_src_rowptr,
@@ -281,12 +274,10 @@ extern "C" int glx_graph_set_row_transform(glx_graph* g, const double* row_scale
   g->d_row_scale = nullptr;
   if (row_scale && g->n_rows > 0) {
     GLX_POOL(glx_pool_alloc((void**)&g->d_row_scale, (size_t)g->n_rows * 8));
-    glx_work* w = nullptr;             // (a work set's stream, not a blocking copy on the NULL stream: see glx_graph_set_order)
-    int rc = glx_work_acquire(g->device, &w);
-    if (rc) return rc;
-    struct WorkGuard { glx_work* w; ~WorkGuard() { hipStreamSynchronize(w->stream); glx_work_release(w); } } wguard{w};
-    GLX_UP(glx_upload(g->d_row_scale, row_scale, (size_t)g->n_rows * 8, w->stream, __func__));
-    GLX_HIP(hipStreamSynchronize(w->stream));
+    GlxCall call;                      // (a work set's stream, not a blocking copy on the NULL stream: see glx_graph_set_order)
+    GLX_UP(call.begin(g->device));
+    GLX_UP(glx_upload(g->d_row_scale, row_scale, (size_t)g->n_rows * 8, call.stream(), __func__));
+    GLX_HIP(hipStreamSynchronize(call.stream()));
   }
   return GLX_OK;
 }
@@ -617,13 +608,11 @@ extern "C" int glx_graph_set_order(glx_graph* g, const int32_t* perm) {
   GLX_POOL(glx_pool_alloc((void**)&g->d_inv, std::max<size_t>(n * 4, 4)));
   // through a work set's stream and its page-locked staging: a blocking hipMemcpy runs on the NULL stream, whose copy queue the first
   // such call of a process creates (9 ms of a fresh model's first fit_predict)
-  glx_work* w = nullptr;
-  int rc = glx_work_acquire(g->device, &w);
-  if (rc) return rc;
-  struct WorkGuard { glx_work* w; ~WorkGuard() { hipStreamSynchronize(w->stream); glx_work_release(w); } } wguard{w};
-  GLX_UP(glx_upload(g->d_perm, g->h_perm.data(), (size_t)n * 4, w->stream, __func__));
-  GLX_UP(glx_upload(g->d_inv, g->h_inv.data(), (size_t)n * 4, w->stream, __func__));
-  GLX_HIP(hipStreamSynchronize(w->stream));
+  GlxCall call;
+  GLX_UP(call.begin(g->device));
+  GLX_UP(glx_upload(g->d_perm, g->h_perm.data(), (size_t)n * 4, call.stream(), __func__));
+  GLX_UP(glx_upload(g->d_inv, g->h_inv.data(), (size_t)n * 4, call.stream(), __func__));
+  GLX_HIP(hipStreamSynchronize(call.stream()));
   return GLX_OK;
 }
 
@@ -885,28 +874,21 @@ int glx_graph_plan(glx_graph* g, int G, SellPlan** out, bool relaxed) {
   GLX_POOL(glx_pool_alloc((void**)&p.d_slice_hdr, std::max<size_t>(16, hdr.size() * sizeof(SliceHdr))));
   GLX_POOL(glx_pool_alloc((void**)&p.d_col, std::max<size_t>(4, (head + stored) * 4)));
   GLX_POOL(glx_pool_alloc((void**)&p.d_val, std::max<size_t>(8, (head + stored) * es)));
-  glx_work* pw = nullptr;              // uploads and the fill run in a work set's stream (no blocking copies on the NULL stream)
-  {
-    int rcw = glx_work_acquire(g->device, &pw);
-    if (rcw) return rcw;
-  }
-  struct WorkGuard { glx_work* w; ~WorkGuard() { hipStreamSynchronize(w->stream); glx_work_release(w); } } pwguard{pw};
-  hipStream_t pst = pw->stream;
+  GlxCall call;                        // uploads and the fill run in a work set's stream (no blocking copies on the NULL stream)
+  GLX_UP(call.begin(g->device));
+  hipStream_t pst = call.stream();
   GLX_UP(glx_upload(p.d_slot_row, slot_row.data(), slot_row.size() * 4, pst, __func__));
   GLX_UP(glx_upload(p.d_slot_len, slot_len.data(), slot_len.size() * 4, pst, __func__));
   GLX_UP(glx_upload(p.d_slice_hdr, hdr.data(), hdr.size() * sizeof(SliceHdr), pst, __func__));
   if (nslices > 0) {
-    // the CSR arrays as they are: resident on the device already (glx_graph_create_resident), or uploaded into work buffers from
-    // the pool that are released after the fill
+    // the CSR arrays as they are: resident on the device already (glx_graph_create_resident), or uploaded into work buffers of
+    // this call
     int32_t *d_rp = g->d_src_rowptr, *d_cc = g->d_src_col;
     double* d_cv = g->d_src_val;
-    struct Tmp { void *a = nullptr, *b = nullptr, *c = nullptr; ~Tmp() { glx_pool_free(a); glx_pool_free(b); glx_pool_free(c); } } tmp;
     if (!d_cc) {
-      int rc2 = glx_pool_alloc(&tmp.a, (size_t)(n + 1) * 4);
-      if (!rc2) rc2 = glx_pool_alloc(&tmp.b, std::max<size_t>((size_t)g->nnz * 4, 4));
-      if (!rc2) rc2 = glx_pool_alloc(&tmp.c, std::max<size_t>((size_t)g->nnz * 8, 8));
-      if (rc2) return rc2;
-      d_rp = (int32_t*)tmp.a; d_cc = (int32_t*)tmp.b; d_cv = (double*)tmp.c;
+      GLX_UP(call.alloc(&d_rp, (size_t)(n + 1)));
+      GLX_UP(call.alloc(&d_cc, (size_t)g->nnz));
+      GLX_UP(call.alloc(&d_cv, (size_t)g->nnz));
       GLX_UP(glx_upload(d_rp, g->h_rowptr.data(), (size_t)(n + 1) * 4, pst, __func__));
       if (g->nnz > 0) {
         GLX_UP(glx_upload(d_cc, g->h_col.data(), (size_t)g->nnz * 4, pst, __func__));
@@ -925,9 +907,8 @@ int glx_graph_plan(glx_graph* g, int G, SellPlan** out, bool relaxed) {
                          (const int32_t*)p.d_slot_len, (const SliceHdr*)p.d_slice_hdr, nslices, head, G, p.d_col, (float*)p.d_val,
                          (const double*)g->d_row_scale, g->reverse_rows ? 1 : 0);
     GLX_HIP(hipGetLastError());
-    GLX_HIP(hipStreamSynchronize(pst));       // the pooled CSR copies go back before anybody else may draw them
   }
-  GLX_HIP(hipStreamSynchronize(pst));         // the host vectors of the plan may go
+  GLX_HIP(hipStreamSynchronize(pst));         // the host vectors of the plan may go; the pooled CSR copies go back when `call` ends
   lap("uploaded");
   g->plans.push_back(p);
   *out = &g->plans.back();

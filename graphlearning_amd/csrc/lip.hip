@@ -22,10 +22,12 @@
 // cleared by a kernel).
 #include "glx_internal.h"
 #include "lip_plan.h"
+#include "glx_stops.h"
 #include <algorithm>
 #include <vector>
 
 static const int LIP_REG_ROW = 32;         // weighted form: rows of up to this many entries are held in registers through the bisection
+static const int LIP_STOP_AFTER = 20;       // no column stops after a sweep <= this one (lp_iterate.cpp:184, :256)
 static const int LIP_LDS_COLS = 64;        // up to this many columns a workgroup folds its errors in LDS before it touches the slots
 
 // The weighted update of a row of at most CAP entries: its values and weights stay in registers through the 30 passes (same entries,
@@ -127,7 +129,7 @@ __device__ __forceinline__ unsigned long long lip_visit(double* u, const int64_t
                                                         const double* __restrict__ W, int32_t v, int B, int b, double alpha, double beta,
                                                         int it, int r, double tol, const unsigned long long* err) {
 #pragma clang fp contract(off)
-  if (it >= 1 && it - 1 > 20 && __longlong_as_double((long long)err[(int64_t)(r - 1) * B + b]) < tol) return 0ull;      // the column has stopped
+  if (it >= 1 && it - 1 > LIP_STOP_AFTER && __longlong_as_double((long long)err[(int64_t)(r - 1) * B + b]) < tol) return 0ull;      // the column has stopped
   const double ne = lip_new_value<WEIGHTED>(u, nbr, W, row_ptr[v], row_ptr[v + 1], B, b, alpha, beta);
   const int64_t at = (int64_t)v * B + b;
   const double d = u[at] - ne;
@@ -203,81 +205,40 @@ __global__ __launch_bounds__(256) void lip_init_kernel(double* u, const int32_t*
   u[t] = q >= 0 ? val[(int64_t)q * B + (t - i * B)] : 0.0;
 }
 
-// the slots of a new chunk: slot 0 <- the last slot of the chunk before (prev_len sweeps; 0: the first chunk), the others <- 0
-__global__ __launch_bounds__(256) void lip_slots_kernel(unsigned long long* err, int B, int prev_len) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  const unsigned long long carry = prev_len > 0 ? err[(int64_t)prev_len * B + b] : 0ull;
-  for (int r = 1; r <= LIP_CHUNK; ++r) err[(int64_t)r * B + b] = 0ull;
-  err[b] = carry;
-}
-
 namespace {
-struct LipBufs {
-  void* p[12] = {};
-  int np = 0;
-  glx_work* work = nullptr;
-  hipStream_t stream = nullptr;
-  int alloc(void** out, size_t bytes) {
-    const int rc = glx_pool_alloc(out, std::max<size_t>((bytes + 7) & ~(size_t)7, 8));
-    if (!rc) p[np++] = *out;
-    return rc;
-  }
-  ~LipBufs() {
-    if (stream) hipStreamSynchronize(stream);   // pooled blocks are reused at once
-    for (int i = 0; i < np; ++i) glx_pool_free(p[i]);
-    glx_work_release(work);
-  }
-};
-
 template <bool WEIGHTED>
 int lip_run(int64_t n, int64_t M, const std::vector<int64_t>& row_ptr, const int32_t* nbr, const double* W, const LipPlan& plan, int B,
             int64_t m, const std::vector<int32_t>& bdy_q, const double* val, double alpha, double beta, int64_t T, double tol, double* u,
             int64_t* iters_out, double* hist, int64_t* launches_out, int device) {
-  GLX_HIP(hipSetDevice(device));
-  LipBufs b;
-  {
-    const int rcw = glx_work_acquire(device, &b.work);
-    if (rcw) return rcw;
-  }
-  hipStream_t st = b.stream = b.work->stream;
+  GlxCall call;
+  GLX_UP(call.begin(device));
+  hipStream_t st = call.stream();
   const int64_t total = n * B, nlv = plan.nlevels, nord = (int64_t)plan.order.size();
   double *d_u = nullptr, *d_w = nullptr, *d_val = nullptr;
   int64_t *d_ptr = nullptr, *d_lvl = nullptr;
   int32_t *d_nbr = nullptr, *d_order = nullptr, *d_bq = nullptr;
   unsigned long long *d_err = nullptr, *stage = nullptr;
-  GLX_UP(b.alloc((void**)&d_u, (size_t)total * 8));
-  GLX_UP(b.alloc((void**)&d_ptr, (size_t)(n + 1) * 8));
-  GLX_UP(b.alloc((void**)&d_nbr, (size_t)M * 4));
-  GLX_UP(b.alloc((void**)&d_w, (size_t)M * 8));
-  GLX_UP(b.alloc((void**)&d_order, (size_t)nord * 4));
-  GLX_UP(b.alloc((void**)&d_lvl, (size_t)(nlv + 1) * 8));
-  GLX_UP(b.alloc((void**)&d_bq, (size_t)n * 4));
-  GLX_UP(b.alloc((void**)&d_val, (size_t)m * B * 8));
-  GLX_UP(b.alloc((void**)&d_err, (size_t)(LIP_CHUNK + 1) * B * 8));
-  GLX_UP(glx_work_stage(b.work, (size_t)LIP_CHUNK * B * 8, (void**)&stage));
-  GLX_UP(glx_upload(d_ptr, row_ptr.data(), (size_t)(n + 1) * 8, st, __func__));
-  if (M > 0) {
-    GLX_UP(glx_upload(d_nbr, nbr, (size_t)M * 4, st, __func__));
-    GLX_UP(glx_upload(d_w, W, (size_t)M * 8, st, __func__));
-  }
-  if (nord > 0) GLX_UP(glx_upload(d_order, plan.order.data(), (size_t)nord * 4, st, __func__));
-  GLX_UP(glx_upload(d_lvl, plan.lvl_ptr.data(), (size_t)(nlv + 1) * 8, st, __func__));
-  GLX_UP(glx_upload(d_bq, bdy_q.data(), (size_t)n * 4, st, __func__));
-  if (m > 0) GLX_UP(glx_upload(d_val, val, (size_t)m * B * 8, st, __func__));
+  GLX_UP(call.alloc(&d_u, (size_t)total));
+  GLX_UP(call.put(&d_ptr, row_ptr.data(), (size_t)(n + 1), __func__));
+  GLX_UP(call.put(&d_nbr, nbr, (size_t)M, __func__));
+  GLX_UP(call.put(&d_w, W, (size_t)M, __func__));
+  GLX_UP(call.put(&d_order, plan.order.data(), (size_t)nord, __func__));
+  GLX_UP(call.put(&d_lvl, plan.lvl_ptr.data(), (size_t)(nlv + 1), __func__));
+  GLX_UP(call.put(&d_bq, bdy_q.data(), (size_t)n, __func__));
+  GLX_UP(call.put(&d_val, val, (size_t)m * B, __func__));
+  GLX_UP(call.alloc(&d_err, (size_t)(LIP_CHUNK + 1) * B));
+  GLX_UP(call.stage(&stage, (size_t)LIP_CHUNK * B));
   hipLaunchKernelGGL(lip_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_u, (const int32_t*)d_bq,
                      (const double*)d_val, n, B);
   GLX_HIP(hipGetLastError());
 
-  std::vector<int64_t> iters((size_t)B, -1);      // sweeps done by a column that has stopped
-  int64_t running = nord > 0 ? B : 0, it = 0, launches = 0;
-  int prev_len = 0;
-  while (it < T && running > 0) {
-    const int len = (int)std::min<int64_t>(LIP_CHUNK, T - it);
-    hipLaunchKernelGGL(lip_slots_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, d_err, B, prev_len);
-    GLX_HIP(hipGetLastError());
+  GlxStops stops(B, T, tol, LIP_STOP_AFTER, hist);
+  if (nord == 0) stops.running = 0;
+  int64_t launches = 0;
+  for (int len; (len = stops.next_len(LIP_CHUNK)) > 0;) {
+    GLX_UP(glx_slots_next_async(d_err, B, LIP_CHUNK, stops.prev_len, st));
     for (int r = 1; r <= len; ++r) {
-      const int sweep = (int)(it + r - 1);
+      const int sweep = (int)(stops.it + r - 1);
       for (const LipLaunch& L : plan.launches) {
         if (L.merged) {
           hipLaunchKernelGGL((lip_merged_kernel<WEIGHTED>), dim3(1), dim3(LIP_BLOCK), 0, st, d_u, (const int64_t*)d_ptr, (const int32_t*)d_nbr,
@@ -295,30 +256,19 @@ int lip_run(int64_t n, int64_t M, const std::vector<int64_t>& row_ptr, const int
     }
     GLX_HIP(hipMemcpyAsync(stage, d_err + B, (size_t)len * B * 8, hipMemcpyDeviceToHost, st));
     GLX_HIP(hipStreamSynchronize(st));
-    for (int r = 1; r <= len; ++r) {
-      const int64_t sweep = it + r - 1;
-      for (int c = 0; c < B; ++c) {
-        if (iters[c] >= 0) continue;
-        const double e = __builtin_bit_cast(double, stage[(size_t)(r - 1) * B + c]);
-        if (hist) hist[sweep * B + c] = e;
-        if (e < tol && sweep > 20) {                   // lp_iterate.cpp:184, :256
-          iters[c] = sweep + 1;
-          --running;
-        }
-      }
-    }
-    it += len;
-    prev_len = len;
+    stops.decide(stage, len);
   }
-  // with no vertex to update the reference still walks its T sweeps (err = 0 throughout) and stops after sweep 21
+  // sweeps done by a column: the stopping sweep counts.  With no vertex to update the reference still walks its T sweeps (err = 0
+  // throughout) and stops after sweep 21
+  std::vector<int64_t> iters((size_t)B);
   for (int c = 0; c < B; ++c) {
     if (nord == 0) {
-      const int64_t done = (T > 22 && 0.0 < tol) ? 22 : T;
+      const int64_t done = (T > LIP_STOP_AFTER + 2 && 0.0 < tol) ? LIP_STOP_AFTER + 2 : T;
       if (hist)
         for (int64_t s = 0; s < done; ++s) hist[s * B + c] = 0.0;
       iters[c] = done;
-    } else if (iters[c] < 0) {
-      iters[c] = T;
+    } else {
+      iters[c] = stops.stop[c] >= 0 ? stops.stop[c] + 1 : T;
     }
   }
   GLX_UP(glx_download(u, d_u, (size_t)total * 8, st, __func__));

@@ -23,11 +23,13 @@
 #include <cstdio>
 #include <limits>
 #include <vector>
+#include "glx_stops.h"
 
 static const int LP_BLOCK = 256;           // threads per workgroup of the batched sweep
 static const int LP_BATCH_CHUNK = 64;      // iterations enqueued between two reads of the error slots
 static const int LP_LDS_COLS = 64;         // up to this many columns a workgroup folds its gaps in LDS before it touches the slots
 static const int LP_MAX_COLS = 256;        // columns per call (the cap of the CG solvers)
+static const int LP_STOP_AFTER = 10;       // no column stops at an iteration <= this one (lp_iterate.cpp:113)
 
 struct LpPlan {
   std::vector<int64_t> start;     // (n + 1) vertex i's entries are start[i] .. start[i + 1] of the sorted list
@@ -72,7 +74,7 @@ inline int lp_make_plan(int64_t n, int64_t M, const int32_t* nbr, const int32_t*
     return 2;
   }
   LpPlan& P = *out;
-  // vertex blocks of the sorted entry list, inverse degrees, largest weight: lp_iterate.cpp:43-64, the expressions of glx_lp_iterate
+  // vertex blocks of the sorted entry list, inverse degrees, largest weight: lp_iterate.cpp:43-64
   P.alpha = 1 / p;
   P.delta = 1 - 2 / p;
   double dt = 0.9 / (P.alpha + 2 * P.delta);
@@ -112,7 +114,7 @@ inline int lp_make_plan(int64_t n, int64_t M, const int32_t* nbr, const int32_t*
 
 // has the column of this slot stopped before iteration `it`?  prev: the slot of iteration it - 1
 constexpr bool lp_frozen(int64_t it, unsigned long long prev, double tol) {
-  return it >= 1 && it - 1 > 10 && __builtin_bit_cast(double, prev) < tol;
+  return it >= 1 && it - 1 > LP_STOP_AFTER && __builtin_bit_cast(double, prev) < tol;
 }
 
 // the slots (chunk + 1, B) of a new chunk: slot 0 <- the last slot of the chunk before (prev_len iterations; 0: the first chunk), the
@@ -125,36 +127,9 @@ inline void lp_slots_next(unsigned long long* slots, int B, int chunk, int prev_
   }
 }
 
-// The host's side of the chunked schedule: how long the next chunk is, and who has stopped where after its slots were read.
-struct LpStops {
-  int B;
-  int64_t T, it = 0;            // `it`: iterations enqueued so far
-  double tol;
-  int running, prev_len = 0;
-  std::vector<int64_t> stop;    // per column: the stopping iteration, -1 while it runs
-  LpStops(int B_, int64_t T_, double tol_) : B(B_), T(T_), tol(tol_), running(B_), stop((size_t)B_, -1) {}
-  // iterations of the next chunk (0: every column has stopped or T is reached)
-  int next_len(int chunk) const {
-    if (running <= 0 || it >= T) return 0;
-    return (int)((T - it < chunk) ? T - it : chunk);
-  }
-  // slots 1 .. len of the chunk that started at iteration `it`, (len, B) row-major
-  void decide(const unsigned long long* slots, int len) {
-    for (int r = 0; r < len; ++r) {
-      const int64_t q = it + r;
-      for (int b = 0; b < B; ++b) {
-        if (stop[b] >= 0) continue;
-        const double e = __builtin_bit_cast(double, slots[(size_t)r * B + b]);
-        if (e < tol && q > 10) {     // lp_iterate.cpp:113
-          stop[b] = q;
-          --running;
-        }
-      }
-    }
-    it += len;
-    prev_len = len;
-  }
-  int64_t iters(int b) const { return stop[b] >= 0 ? stop[b] : T; }
+// the chunk schedule and stop decision of this iteration: GlxStops with the reference's `it > 10`
+struct LpStops : GlxStops {
+  LpStops(int B_, int64_t T_, double tol_) : GlxStops(B_, T_, tol_, LP_STOP_AFTER) {}
 };
 
 // which iterate U_k the first buffer (what the call returns) holds for a column with this stopping iteration (`stop` = T: never stopped)

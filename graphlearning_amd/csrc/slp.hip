@@ -92,31 +92,6 @@ __global__ void slp_base_kernel(int64_t* base, int64_t it) {
   if (threadIdx.x == 0 && blockIdx.x == 0) base[0] = it;
 }
 
-namespace {
-struct SlpBufs {
-  void* p[16] = {};
-  int np = 0;
-  glx_work* work = nullptr;
-  hipStream_t stream = nullptr;
-  hipGraphExec_t exec = nullptr;
-  int alloc(void** out, size_t bytes) {
-    const int rc = glx_pool_alloc(out, std::max<size_t>((bytes + 7) & ~(size_t)7, 8));
-    if (!rc) p[np++] = *out;
-    return rc;
-  }
-  void drop_exec() {
-    if (exec) hipGraphExecDestroy(exec);
-    exec = nullptr;
-  }
-  ~SlpBufs() {
-    if (stream) hipStreamSynchronize(stream);   // pooled blocks are reused at once
-    drop_exec();
-    for (int i = 0; i < np; ++i) glx_pool_free(p[i]);
-    glx_work_release(work);
-  }
-};
-}  // namespace
-
 extern "C" int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* W, const double* lam,
                                const double* gamma, int C, int64_t m, const int32_t* ind, const double* val, int64_t T, double* u,
                                double* u_hist, int64_t* plan_out, int device) {
@@ -135,37 +110,29 @@ extern "C" int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, con
   const std::vector<SlpTile> tiles = slp_tiles(C);
   const int cpad_max = tiles[0].cpad;               // the first tile is the widest
 
-  GLX_HIP(hipSetDevice(device));
-  SlpBufs b;
-  GLX_UP(glx_work_acquire(device, &b.work));
-  hipStream_t st = b.stream = b.work->stream;
+  GlxCall call;
+  GLX_UP(call.begin(device));
+  hipStream_t st = call.stream();
   int64_t *d_ptr = nullptr, *d_base = nullptr;
   int32_t *d_col = nullptr, *d_rev = nullptr, *d_lab = nullptr;
   double *d_w = nullptr, *d_lam = nullptr, *d_gamma = nullptr, *d_val = nullptr, *d_Y = nullptr, *d_u = nullptr, *d_ut = nullptr,
          *d_out = nullptr, *d_hist = nullptr;
   const size_t hist_bytes = u_hist ? (size_t)T * n * C * 8 : 0;
-  GLX_UP(b.alloc((void**)&d_ptr, (size_t)(n + 1) * 8));
-  GLX_UP(b.alloc((void**)&d_col, (size_t)M * 4));
-  GLX_UP(b.alloc((void**)&d_rev, (size_t)M * 4));
-  GLX_UP(b.alloc((void**)&d_lab, (size_t)n * 4));
-  GLX_UP(b.alloc((void**)&d_w, (size_t)M * 8));
-  GLX_UP(b.alloc((void**)&d_lam, (size_t)M * 8));
-  GLX_UP(b.alloc((void**)&d_gamma, (size_t)n * 8));
-  GLX_UP(b.alloc((void**)&d_val, (size_t)std::max<int64_t>(m, 1) * C * 8));
-  GLX_UP(b.alloc((void**)&d_Y, (size_t)M * cpad_max * 8));
-  GLX_UP(b.alloc((void**)&d_u, (size_t)n * cpad_max * 8));
-  GLX_UP(b.alloc((void**)&d_ut, (size_t)n * cpad_max * 8));
-  GLX_UP(b.alloc((void**)&d_out, (size_t)n * C * 8));
-  GLX_UP(b.alloc((void**)&d_base, 8));
-  if (hist_bytes) GLX_UP(b.alloc((void**)&d_hist, hist_bytes));
-  GLX_UP(glx_upload(d_ptr, row_ptr, (size_t)(n + 1) * 8, st, __func__));
-  GLX_UP(glx_upload(d_col, col, (size_t)M * 4, st, __func__));
-  GLX_UP(glx_upload(d_rev, rev.data(), (size_t)M * 4, st, __func__));
-  GLX_UP(glx_upload(d_lab, lab.data(), (size_t)n * 4, st, __func__));
-  GLX_UP(glx_upload(d_w, W, (size_t)M * 8, st, __func__));
-  GLX_UP(glx_upload(d_lam, lam, (size_t)M * 8, st, __func__));
-  GLX_UP(glx_upload(d_gamma, gamma, (size_t)n * 8, st, __func__));
+  GLX_UP(call.put(&d_ptr, row_ptr, (size_t)(n + 1), __func__));
+  GLX_UP(call.put(&d_col, col, (size_t)M, __func__));
+  GLX_UP(call.put(&d_rev, (const int32_t*)rev.data(), (size_t)M, __func__));
+  GLX_UP(call.put(&d_lab, lab.data(), (size_t)n, __func__));
+  GLX_UP(call.put(&d_w, W, (size_t)M, __func__));
+  GLX_UP(call.put(&d_lam, lam, (size_t)M, __func__));
+  GLX_UP(call.put(&d_gamma, gamma, (size_t)n, __func__));
+  GLX_UP(call.alloc(&d_val, (size_t)std::max<int64_t>(m, 1) * C));
   if (m > 0) GLX_UP(glx_upload(d_val, val, (size_t)m * C * 8, st, __func__));
+  GLX_UP(call.alloc(&d_Y, (size_t)M * cpad_max));
+  GLX_UP(call.alloc(&d_u, (size_t)n * cpad_max));
+  GLX_UP(call.alloc(&d_ut, (size_t)n * cpad_max));
+  GLX_UP(call.alloc(&d_out, (size_t)n * C));
+  GLX_UP(call.alloc(&d_base, 1));
+  if (hist_bytes) GLX_UP(call.alloc(&d_hist, hist_bytes / 8));
 
   int64_t launches = 0;
   for (const SlpTile& tile : tiles) {
@@ -187,7 +154,7 @@ extern "C" int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, con
     };
     // a captured sequence pays for itself from the second replay on
     const bool replay = T >= 2 * (int64_t)SLP_CHUNK;
-    b.drop_exec();
+    call.drop_exec();
     for (int64_t it = 0; it < T;) {
       const int len = (int)std::min<int64_t>(SLP_CHUNK, T - it);
       if (d_hist) {
@@ -195,7 +162,7 @@ extern "C" int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, con
         GLX_HIP(hipGetLastError());
       }
       if (replay && len == SLP_CHUNK) {
-        if (!b.exec) {
+        if (!call.exec) {
           hipGraph_t graph = nullptr;
           const int64_t before = launches;
           GLX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -205,11 +172,11 @@ extern "C" int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, con
           launches = before;
           if (rc2) { if (graph) hipGraphDestroy(graph); return rc2; }
           GLX_HIP(e);
-          const hipError_t e2 = hipGraphInstantiate(&b.exec, graph, nullptr, nullptr, 0);
+          const hipError_t e2 = hipGraphInstantiate(&call.exec, graph, nullptr, nullptr, 0);
           hipGraphDestroy(graph);
           GLX_HIP(e2);
         }
-        GLX_HIP(hipGraphLaunch(b.exec, st));
+        GLX_HIP(hipGraphLaunch(call.exec, st));
         launches += 2 * SLP_CHUNK;
       } else {
         for (int r = 0; r < len; ++r) GLX_UP(enqueue(r));

@@ -187,23 +187,6 @@ __global__ __launch_bounds__(256) void sssp_cp_finish_kernel(int32_t* cp, int64_
 }
 
 namespace {
-struct SsspBufs {
-  void* p[16] = {};
-  int np = 0;
-  glx_work* work = nullptr;
-  hipStream_t stream = nullptr;
-  int alloc(void** out, size_t bytes) {
-    const int rc = glx_pool_alloc(out, std::max<size_t>((bytes + 7) & ~(size_t)7, 8));
-    if (!rc) p[np++] = *out;
-    return rc;
-  }
-  ~SsspBufs() {
-    if (stream) hipStreamSynchronize(stream);   // pooled blocks are reused at once
-    for (int i = 0; i < np; ++i) glx_pool_free(p[i]);
-    glx_work_release(work);
-  }
-};
-
 // Rounds until one changes nothing.  launch(r) enqueues round r of a chunk (r = 1 .. SSSP_CHUNK).  rounds_out: rounds run, the
 // idle last one included.
 template <class F>
@@ -236,13 +219,9 @@ template <int FORM, bool ACT>
 int sssp_run(int64_t n, int64_t nnz, const int64_t* in_ptr, const int32_t* in_idx, const double* in_cost, const int64_t* out_ptr,
              const int32_t* out_idx, int B, int64_t m, const int32_t* src, const int32_t* prob, const double* val, double max_dist,
              double* dist, int32_t* cp, int64_t* rounds_out, double* ms_out, int device) {
-  GLX_HIP(hipSetDevice(device));
-  SsspBufs b;
-  {
-    const int rcw = glx_work_acquire(device, &b.work);
-    if (rcw) return rcw;
-  }
-  hipStream_t st = b.stream = b.work->stream;
+  GlxCall call;
+  GLX_UP(call.begin(device));
+  hipStream_t st = call.stream();
   const auto t_start = std::chrono::steady_clock::now();
   auto ms_since = [](std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -255,21 +234,21 @@ int sssp_run(int64_t n, int64_t nnz, const int64_t* in_ptr, const int32_t* in_id
   double *d_cost = nullptr, *d_val = nullptr;
   unsigned char* d_act = nullptr;
   unsigned long long *d_flags = nullptr, *stage = nullptr;
-  GLX_UP(b.alloc((void**)&d_u, (size_t)total * 8));
-  if (cp) GLX_UP(b.alloc((void**)&d_cp, (size_t)total * 4));
-  GLX_UP(b.alloc((void**)&d_ptr, (size_t)(n + 1) * 8));
-  GLX_UP(b.alloc((void**)&d_idx, (size_t)nnz * 4));
-  GLX_UP(b.alloc((void**)&d_cost, (size_t)nnz * 8));
-  GLX_UP(b.alloc((void**)&d_src, (size_t)m * 4));
-  GLX_UP(b.alloc((void**)&d_prob, (size_t)m * 4));
-  GLX_UP(b.alloc((void**)&d_val, (size_t)m * 8));
-  GLX_UP(b.alloc((void**)&d_flags, (size_t)(SSSP_CHUNK + 1) * 8));
+  GLX_UP(call.alloc(&d_u, (size_t)total));
+  if (cp) GLX_UP(call.alloc(&d_cp, (size_t)total));
+  GLX_UP(call.alloc(&d_ptr, (size_t)(n + 1)));
+  GLX_UP(call.alloc(&d_idx, (size_t)nnz));
+  GLX_UP(call.alloc(&d_cost, (size_t)nnz));
+  GLX_UP(call.alloc(&d_src, (size_t)m));
+  GLX_UP(call.alloc(&d_prob, (size_t)m));
+  GLX_UP(call.alloc(&d_val, (size_t)m));
+  GLX_UP(call.alloc(&d_flags, (size_t)SSSP_CHUNK + 1));
   if (ACT) {
-    GLX_UP(b.alloc((void**)&d_optr, (size_t)(n + 1) * 8));
-    GLX_UP(b.alloc((void**)&d_oidx, (size_t)nnz * 4));
-    GLX_UP(b.alloc((void**)&d_act, (size_t)total * 2));
+    GLX_UP(call.alloc(&d_optr, (size_t)(n + 1)));
+    GLX_UP(call.alloc(&d_oidx, (size_t)nnz));
+    GLX_UP(call.alloc(&d_act, (size_t)total * 2));
   }
-  GLX_UP(glx_work_stage(b.work, (size_t)SSSP_CHUNK * 8, (void**)&stage));
+  GLX_UP(call.stage(&stage, (size_t)SSSP_CHUNK));
   GLX_UP(glx_upload(d_ptr, in_ptr, (size_t)(n + 1) * 8, st, __func__));
   if (ACT) GLX_UP(glx_upload(d_optr, out_ptr, (size_t)(n + 1) * 8, st, __func__));
   if (nnz > 0) {

@@ -154,23 +154,16 @@ __global__ void exp_cr_kernel(const double* __restrict__ x, double* __restrict__
 extern "C" int glx_exp_cr(const double* x, double* out, int64_t n, int device) {
   GLX_CHECK((x && out) || n == 0, GLX_EINVAL, "glx_exp_cr: null argument");
   if (n <= 0) return GLX_OK;
-  GLX_HIP(hipSetDevice(device));
+  GlxCall call;
+  GLX_UP(call.begin(device));
   double *dx = nullptr, *dy = nullptr;
-  int rc = glx_pool_alloc((void**)&dx, (size_t)n * 8);
-  if (!rc) rc = glx_pool_alloc((void**)&dy, (size_t)n * 8);
-  if (!rc) {
-    rc = glx_upload_sync(dx, x, (size_t)n * 8, "glx_exp_cr");
-    hipError_t e = hipSuccess;
-    if (!rc) {
-      hipLaunchKernelGGL(exp_cr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const double*)dx, dy, n);
-      e = hipGetLastError();
-      if (e == hipSuccess) rc = glx_download_sync(out, dy, (size_t)n * 8, "glx_exp_cr");
-    }
-    if (!rc && e != hipSuccess) { glx_set_error("glx_exp_cr: %s", hipGetErrorString(e)); rc = GLX_EHIP; }
-  }
-  glx_pool_free(dx);
-  glx_pool_free(dy);
-  return rc;
+  GLX_UP(call.alloc(&dx, (size_t)n));
+  GLX_UP(call.alloc(&dy, (size_t)n));
+  GLX_UP(glx_upload_sync(dx, x, (size_t)n * 8, "glx_exp_cr"));
+  hipLaunchKernelGGL(exp_cr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const double*)dx, dy, n);
+  const hipError_t e = hipGetLastError();
+  GLX_CHECK(e == hipSuccess, GLX_EHIP, "glx_exp_cr: %s", hipGetErrorString(e));
+  return glx_download_sync(out, dy, (size_t)n * 8, "glx_exp_cr");
 }
 
 __global__ __launch_bounds__(256) void glx_zero_kernel(unsigned long long* __restrict__ p, int64_t nwords) {
@@ -182,6 +175,19 @@ int glx_zero_async(void* p, size_t bytes, hipStream_t st) {
   const int64_t nw = (int64_t)(bytes / 8);
   hipLaunchKernelGGL(glx_zero_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (nw + 255) / 256))), dim3(256), 0, st,
                      (unsigned long long*)p, nw);
+  GLX_HIP(hipGetLastError());
+  return GLX_OK;
+}
+
+__global__ __launch_bounds__(256) void glx_slots_next_kernel(unsigned long long* err, int B, int chunk, int prev_len) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long carry = prev_len > 0 ? err[(int64_t)prev_len * B + b] : 0ull;
+  for (int r = 1; r <= chunk; ++r) err[(int64_t)r * B + b] = 0ull;
+  err[b] = carry;
+}
+int glx_slots_next_async(unsigned long long* err, int B, int chunk, int prev_len, hipStream_t st) {
+  hipLaunchKernelGGL(glx_slots_next_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, err, B, chunk, prev_len);
   GLX_HIP(hipGetLastError());
   return GLX_OK;
 }

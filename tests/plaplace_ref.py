@@ -81,21 +81,27 @@ def start_values(n, ind, val):
     return np.ascontiguousarray(uu), np.ascontiguousarray(ul)
 
 
-def oracle_column(n, I, J, V, ind, val, p, T, tol):
-    """(uu, ul, stopping iteration) of one column."""
+def oracle_from(uu, ul, n, I, J, V, ind, val, p, T, tol):
+    """(uu, ul, stopping iteration) of one column from the given start (copied, not written)."""
     vp = ctypes.c_void_p
     I = np.ascontiguousarray(I, dtype=np.int32)
     J = np.ascontiguousarray(J, dtype=np.int32)
     V = np.ascontiguousarray(V, dtype=np.float64)
     ind = np.ascontiguousarray(ind, dtype=np.int32)
     val = np.ascontiguousarray(val, dtype=np.float64)
-    uu, ul = start_values(n, ind, val)
+    uu, ul = np.array(uu, dtype=np.float64), np.array(ul, dtype=np.float64)
     with np.errstate(all='ignore'):
         it = _oracle_lib().ref_lp_iterate(uu.ctypes.data_as(vp), ul.ctypes.data_as(vp), J.ctypes.data_as(vp), I.ctypes.data_as(vp),
                                           V.ctypes.data_as(vp), ind.ctypes.data_as(vp), val.ctypes.data_as(vp), ctypes.c_double(p),
                                           ctypes.c_int64(int(T)), ctypes.c_double(float(tol)), ctypes.c_int64(n), ctypes.c_int64(len(V)),
                                           ctypes.c_int64(len(ind)))
     return uu, ul, int(it)
+
+
+def oracle_column(n, I, J, V, ind, val, p, T, tol):
+    """(uu, ul, stopping iteration) of one column from the start graph.plaplace sets up."""
+    uu, ul = start_values(n, ind, val)
+    return oracle_from(uu, ul, n, I, J, V, ind, val, p, T, tol)
 
 
 def oracle_batch(n, I, J, V, ind, vals, p, T, tol):

@@ -1,6 +1,6 @@
 """_hip.lp_iterate_batch, graph._plaplace_batch and ssl.plaplace on the device: every column of the batched Jacobi iteration against
 its own _hip.lp_iterate call and against the oracle's restatement on this host (uu, ul and the stopping iteration, bit for bit), the
-golden fits of the compiled reference through the learner, the learner against the existing single-problem paths, ssl_trials, and one
+single call from a start of the caller's own against the oracle, the golden fits of the compiled reference through the learner, the learner against the existing single-problem paths, ssl_trials, and one
 case with the library's buffer pool switched off.
 
 Every test runs under a time limit of its own: a test that exceeds it ends the whole session on the spot (traceback of every
@@ -177,6 +177,37 @@ def test_caps(gl, problems, references, name, B):
             for b in range(B):
                 wu, wl = ref.start_values(n, ind, vals[:, b])
                 assert ref.same(got[0][:, b], wu) and ref.same(got[1][:, b], wl)
+
+
+def test_single_call_from_a_given_start(gl):
+    """_hip.lp_iterate from a start the batched path never forms (off the boundary uu raised and ul lowered, vertex by vertex)
+    against the oracle called with the same arrays: uu and ul bit for bit, the stopping iteration exactly.  The caps lie on both
+    sides of the first possible stop (iteration 11) and return either buffer (even / odd); the run to the stop ends beyond the
+    first chunk of 64 iterations, at another iteration than from the start of graph.plaplace (with this seed 66 against 61 and 63)."""
+    from graphlearning_amd import _hip
+    rng = np.random.default_rng(5)
+    p, tol = 6.0, 1e-2
+    for n in (255, 257):
+        I, J, V = ref.entries(ref.random_graph(n, n))
+        ind = np.sort(rng.choice(n, size=17, replace=False))
+        val = rng.normal(size=17)
+        uu0, ul0 = ref.start_values(n, ind, val)
+        off = np.ones(n, dtype=bool)
+        off[ind] = False
+        uu0[off] += rng.random(n - 17)
+        ul0[off] -= rng.random(n - 17)
+        ind32 = np.ascontiguousarray(ind, dtype=np.int32)
+        for T in (0, 11, 12, 13, 40, 41, 10 ** 6):
+            wu, wl, wit = ref.oracle_from(uu0, ul0, n, I, J, V, ind, val, p, T, tol)
+            uu, ul = uu0.copy(), ul0.copy()
+            it = _hip.lp_iterate(uu, ul, J, I, V, ind32, val, p, T, tol)
+            print(n, T, 'stop', it, 'want', wit)
+            assert it == wit, (n, T, it, wit)
+            assert ref.same(uu, wu) and ref.same(ul, wl), (n, T)
+            assert np.isfinite(wu).all() and np.isfinite(wl).all()
+        default = ref.oracle_column(n, I, J, V, ind, val, p, 10 ** 6, tol)[2]
+        print(n, 'stop from the default start', default)
+        assert wit > 64 and wit != default, (n, wit, default)
 
 
 def test_refused_widths_and_caps(gl, problems):
