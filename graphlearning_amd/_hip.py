@@ -159,6 +159,8 @@ _SIGNATURES = {
     'glx_slp_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
     'glx_lp_iterate_batch': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_double, C.c_int64, C.c_double, _vp, _vp, _vp,
                              C.c_int],
+    'glx_ck_solve': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp,
+                     _f64p, _i64p, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1176,6 +1178,53 @@ def slp_iterate(row_ptr, col, W, lam, gamma, ind, val, T, device=None, want_hist
     check(load().glx_slp_iterate(n, len(col), _ptr(row_ptr), _ptr(col), _ptr(W), _ptr(lam), _ptr(gamma), Cc, len(ind), _ptr(ind), _ptr(val),
                                  T, _ptr(u), _ptr(hist) if (want_history and T > 0) else None, plan, _dev(device)), 'glx_slp_iterate')
     return u, hist, (int(plan[0]), int(plan[1]), int(plan[2]))
+
+
+def ck_solve(row_ptr, col, W, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e-10, max_it=1 << 24, device=None, err_cap=0, on_iterate=None):
+    """The centered-kernel learner's two loops in one device call (glx_ck_solve, csrc/ck.hip; the contract is DESIGN.md 4.11): W as
+    canonical CSR arrays (row_ptr, col, W) without its diagonal, the training vertices `ind` with their start rows `val` (m, k), the
+    power iteration's start vector e (n).  Returns (u (n, k) float64, l, T, err (err_cap values: err_q at [q - 1] for q <= T, NaN behind), plan = (kernels per
+    iteration, launches enqueued, iterations per chunk, partial sums per column)).  on_iterate(q, u_q, err_q), if given, is called after
+    every iteration with a view of the iterate that is valid during the call only; the solve then runs one iteration per chunk and
+    downloads every iterate (slow).  GlxError when max_it iterations pass without a stop."""
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    ind = np.ascontiguousarray(ind, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64).ravel()
+    n = len(row_ptr) - 1
+    if (row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or W.shape != col.shape or ind.ndim != 1 or val.ndim != 2 or val.shape[0] != len(ind)
+            or val.shape[1] < 1 or e.shape != (n,) or int(err_cap) < 0):
+        raise GlxError('ck_solve: inconsistent array shapes or sizes')
+    k = int(val.shape[1])
+    u = np.empty((n, k), dtype=np.float64)
+    errs = np.full(int(err_cap), np.nan)
+    l, T = C.c_double(0.0), C.c_int64(0)
+    plan = (C.c_int64 * 4)(0, 0, 0, 0)
+    raised = []
+    cb = None
+    if on_iterate is not None:
+        def _each(q, ptr, err, _user):
+            try:
+                on_iterate(int(q), np.ctypeslib.as_array(ptr, shape=(n, k)), float(err))
+                return 0
+            except BaseException as exc:      # an exception cannot cross the C frames: end the call and raise it afterwards
+                raised.append(exc)
+                return 1
+        cb = _CK_ITERATE_FN(_each)
+    try:
+        check(load().glx_ck_solve(n, len(col), _ptr(row_ptr), _ptr(col), _ptr(W), k, len(ind), _ptr(ind), _ptr(val), _ptr(e), int(power_it),
+                                  float(alpha_frac), float(tol), int(max_it), _ptr(u), C.byref(l), C.byref(T), _ptr(errs) if err_cap else None,
+                                  int(err_cap), C.cast(cb, _vp) if cb is not None else None, None, plan, _dev(device)), 'glx_ck_solve')
+    except GlxError:
+        if raised:
+            raise raised[0]
+        raise
+    return u, float(l.value), int(T.value), errs, tuple(int(v) for v in plan)
+
+
+_CK_ITERATE_FN = C.CFUNCTYPE(C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_double, _vp)
 
 
 def host_row_sums(W):

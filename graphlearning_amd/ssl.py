@@ -1370,6 +1370,76 @@ class sparse_label_propagation(ssl):
         return u
 
 
+class centered_kernel(ssl):
+    def __init__(self, W=None, class_priors=None, tol=1e-10, power_it=100, alpha=1.05):
+        """Centered kernel method (reference ssl.py:1346-1426; Mai and Couillet, ICML 2018): the power iteration for the largest
+        eigenvalue l of C W C (C centres a column) and the fixed-point iteration u <- u + ((1 / (alpha l)) C W C u - u) off the training
+        rows until max|w| <= tol, all classes as the columns of one device call (_hip.ck_solve; the contract is DESIGN.md 4.11).  Not
+        one-vs-rest.  The start vector of the power iteration is `np.random.rand(n, 1)` from numpy's global stream, drawn with
+        exactly that one call, so a user who seeds as for the reference gets the reference's vector.  The column means are sums
+        over all vertices, whose order in the reference belongs to the host's BLAS: `prob` equals the reference's to a measured
+        1e-15 or so, the iteration count exactly; the result is a pure function of the inputs.  After a fit:
+        `num_iter`, `eigenvalue` (the l it used) and `ck_plan`.  With `all_labels` the reference's line `Accuracy = ..` is printed
+        after every iteration while the solve runs, from iterates downloaded one by one: that path is slow.  The reference has no
+        iteration cap; this loop fails with GlxError after `max_it` (2^24) iterations.  Refused with ValueError before any device
+        call: power_it < 1, a weight that is NaN or infinite, a training index out of range, labels that are not exactly 0 .. k-1,
+        index and label arrays of different lengths, an empty training set, more than 256 classes.  Rows without entries and
+        negative weights are legal."""
+        super().__init__(W, class_priors)
+        self.tol = tol
+        self.power_it = power_it
+        self.alpha = alpha
+        self.max_it = 1 << 24
+        self.accuracy_filename = '_centered_kernel'
+        self.name = 'Centered Kernel'
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        n = self.graph.num_nodes
+        train_ind = np.asarray(train_ind).ravel()
+        train_labels = np.asarray(train_labels).ravel()
+        if not int(self.power_it) >= 1:
+            raise ValueError('centered_kernel: power_it=%r, at least one power iteration is needed' % (self.power_it,))
+        if len(train_ind) != len(train_labels):
+            raise ValueError('centered_kernel: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
+        if len(train_ind) == 0:
+            raise ValueError('centered_kernel: no training vertex')
+        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
+            raise ValueError('centered_kernel: train_ind out of range (or not an integer array)')
+        classes = np.unique(train_labels)
+        k = len(classes)
+        if not np.array_equal(classes, np.arange(k)):
+            raise ValueError('centered_kernel: the labels are not exactly 0 .. %d' % (k - 1))
+        if k > 256:
+            raise ValueError('centered_kernel: %d classes, at most 256 columns per call' % k)
+        W = self.graph.weight_matrix
+        W = sparse.csr_matrix(W - sparse.spdiags(W.diagonal(), 0, n, n), dtype=np.float64)      # the diagonal goes as in the reference
+        W.sum_duplicates()
+        W.eliminate_zeros()
+        W.sort_indices()
+        if not np.all(np.isfinite(W.data)):
+            raise ValueError('centered_kernel: a weight is NaN or infinite')
+        K = np.zeros((n, k))
+        K[train_ind] = (train_labels.astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
+        K[train_ind, :] -= np.sum(K, axis=0) / len(train_ind)
+        # rows listed twice: the device call gives a vertex its last row, as the assignment above does
+        val = np.ascontiguousarray(K[train_ind])
+        e = np.random.rand(n, 1)
+        on_iterate = None
+        if all_labels is not None:
+            def on_iterate(q, u, err):
+                self.prob = np.array(u, copy=True)
+                acc = ssl_accuracy(self.predict(), all_labels, train_ind)
+                sys.stdout.write('Accuracy = %.2f\n' % acc)
+                sys.stdout.flush()
+        u, l, T, _, plan = _hip.ck_solve(W.indptr.astype(np.int64), W.indices.astype(np.int32), W.data, train_ind.astype(np.int32), val, e,
+                                         power_it=int(self.power_it), alpha_frac=float(self.alpha), tol=float(self.tol), max_it=int(self.max_it),
+                                         device=self.device, on_iterate=on_iterate)
+        self.num_iter = T
+        self.eigenvalue = l
+        self.ck_plan = plan
+        return u
+
+
 def ssl_accuracy(pred_labels, true_labels, train_ind):
     """Accuracy in percent over nodes outside train_ind with a true label >= 0
     (reference ssl.py:1795-1834: `100*np.mean(pred[mask] == true[mask])` over the masked arrays).  The same number from

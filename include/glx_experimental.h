@@ -245,6 +245,30 @@ int glx_lp_iterate_batch(int64_t n, int64_t M, const int32_t* nbr, const int32_t
                          const int32_t* ind, const double* val, double p, int64_t T, double tol, double* uu, double* ul,
                          int64_t* iters_out, int device);
 
+/* ---- centered-kernel learner: ssl.centered_kernel (csrc/ck.hip, csrc/ck_plan.h) ---------------------------------------------------
+ * The loop of the reference's ssl.centered_kernel (ssl.py:1346-1426; Mai and Couillet, ICML 2018) in one blocking call: power_it
+ * steps of the power iteration e <- C W C e / |C W C e| from the caller's start vector e (n) for l = |e.w / e.e|, alpha =
+ * alpha_frac * l, then u <- u + w with w = (1 / alpha) C W C u - u, w = 0 on the training rows, until !(max|w| > tol): iteration q
+ * (1-based) is the last one iff !(err_q > tol), with err_0 = 1 (tol >= 1 or NaN: no iteration, u is the start).  C x = x - mean(x)
+ * column by column; the products use the one-pass form and the fixed reduction order of DESIGN.md 4.11, so the result is a pure
+ * function of the arguments (no floating-point atomics) and equals ck_host_reference (csrc/ck_plan.h) bit for bit.  W arrives as
+ * canonical CSR WITHOUT its diagonal: n rows, M entries, row_ptr (n + 1), col ascending inside a row; weights finite, of either sign;
+ * empty rows are legal.  1 <= k <= 256 columns; u starts from val (m, k) row-major on the m training vertices ind (a vertex listed
+ * twice takes its last row) and from zero elsewhere.  Two launches per iteration; the host reads the err slots once per chunk.
+ * u (n, k) row-major: the iterate that includes the stopping iteration's update.  *l_out: the eigenvalue estimate.  *T_out: the
+ * iterations that ran.  err_hist (or NULL): err_q at err_hist[q - 1] for q <= min(T, err_cap); nothing behind it is written.
+ * on_iterate (or NULL): called after every iteration with (q, the iterate (n, k), err_q, user) -- the call then runs one iteration
+ * per chunk and downloads every iterate, which is slow; a nonzero return ends the call with GLX_EINVAL.  plan_out[4] (or NULL):
+ * kernels per iteration, launches enqueued, iterations per chunk, partial sums per column.  All pointers are host pointers.
+ * GLX_EINVAL: a null argument, bad sizes, rows that are not canonical or store a diagonal entry, an index out of range, a weight that is
+ * not finite, power_it or max_it outside [1, 2^24].  GLX_EUNSUPPORTED: k > 256, n * k > 2^31, or max_it iterations without a stop
+ * (the reference has no cap; *l_out is set). */
+typedef int (*glx_ck_iterate_fn)(int64_t q, const double* u, double err, void* user);
+int glx_ck_solve(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* W, int k, int64_t m, const int32_t* ind,
+                 const double* val, const double* e, int64_t power_it, double alpha_frac, double tol, int64_t max_it, double* u,
+                 double* l_out, int64_t* T_out, double* err_hist, int64_t err_cap, glx_ck_iterate_fn on_iterate, void* user,
+                 int64_t* plan_out, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,288 @@
+"""The centered-kernel learner restated in numpy, twice, for tests/test_ck_host.py, tests/test_gpu_ck.py and the fixture generator
+tests/golden/make_golden_ck.py.
+
+`ck_reference_order` is the independent check: the loop of ssl.centered_kernel with the products in the reference's own formula order
+(centre, multiply by W, centre again; the column means as ones-matrix products, whose summation order belongs to the host's BLAS).
+
+`ck_device_order` is the order the device documents (csrc/ck_plan.h), vectorised: the one-pass form
+W u - d (x) m - 1 (x) yb, every operation rounded on its own, row sums entry by entry in stored order, the partial sums of 64 rows by a
+halving tree, the partials by 64 chains and the same tree.  It equals ck_host_reference (csrc/ck_plan.h, built on the host behind
+tests/ck_plan_host.cpp) and the device bit for bit, and returns the err history."""
+import ctypes
+import os
+import subprocess
+import numpy as np
+from scipy import sparse
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN_FILE = 'g18_ck.npz'
+# case -> (graph, classes)
+GOLDEN_CASES = {'blobs': ('blobs', 3), 'directed': ('directed', 3), 'ten': ('ten', 10), 'loops': ('loops', 3), 'tiny': ('tiny', 2)}
+ROWS = 64           # CK_ROWS and CK_CHAINS of ck_plan.h
+MAX_IT = 1 << 24
+
+
+def canonical(W):
+    W = sparse.csr_matrix(W, dtype=np.float64, copy=True)
+    W.sum_duplicates()
+    W.sort_indices()
+    return W
+
+
+def without_diagonal(W):
+    """What the learner hands to the device: the reference's `W - spdiags(W.diagonal())` as canonical CSR without explicit zeros."""
+    n = W.shape[0]
+    W = sparse.csr_matrix(W - sparse.spdiags(W.diagonal(), 0, n, n), dtype=np.float64)
+    W.sum_duplicates()
+    W.eliminate_zeros()
+    W.sort_indices()
+    return W
+
+
+def start_values(n, ind, labels, k):
+    """K (n, k) of the reference: one-hot rows of the training vertices, centred over them, zero elsewhere."""
+    K = np.zeros((n, k))
+    K[ind] = (np.asarray(labels).astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
+    K[ind, :] -= np.sum(K, axis=0) / len(ind)
+    return K
+
+
+# ---- the reference's formula order ---------------------------------------------------------------------------------------------------
+
+def ck_reference_order(W, ind, labels, k, e, power_it=100, alpha=1.05, tol=1e-10, max_it=MAX_IT):
+    """(u, l, T, err history).  W with its diagonal (it is removed here, as the reference does); e (n, 1) the start vector."""
+    n = W.shape[0]
+    W = W - sparse.spdiags(W.diagonal(), 0, n, n)
+    ones_col, ones_row = np.ones((n, 1)), np.ones((1, n))
+
+    def centred_product(x):
+        y = W * (x - (1 / n) * ones_col @ (ones_row @ x))
+        return y - (1 / n) * ones_col @ (ones_row @ y)
+    e = np.array(e, dtype=np.float64).reshape(n, 1)
+    with np.errstate(all='ignore'):
+        for _ in range(power_it):
+            w = centred_product(e)
+            l = abs(np.transpose(e) @ w / (np.transpose(e) @ e))
+            e = w / np.linalg.norm(w)
+        a = alpha * l
+        u = start_values(n, ind, labels, k)
+        errs = []
+        err = 1
+        while err > tol and len(errs) < max_it:
+            w = (1 / a) * centred_product(u) - u
+            w[ind, :] = 0
+            err = np.max(np.absolute(w))
+            u = u + w
+            errs.append(err)
+    return u, float(l[0, 0]), len(errs), np.array(errs, dtype=np.float64)
+
+
+# ---- the device's documented order ---------------------------------------------------------------------------------------------------
+
+def _tree(a):
+    """a (P, 64, q): a[r] += a[r + h] for r < h, h = 32 .. 1"""
+    for h in (32, 16, 8, 4, 2, 1):
+        a = a[:, :h] + a[:, h:2 * h]
+    return a[:, 0]
+
+
+def _partials(v):
+    """v (n, q) -> (P, q): partial p adds rows [64 p, 64 p + 64), rows past n count as +0.0"""
+    n, q = v.shape
+    P = -(-n // ROWS)
+    pad = np.zeros((P * ROWS, q))
+    pad[:n] = v
+    return _tree(pad.reshape(P, ROWS, q))
+
+
+def _finish(part):
+    """part (P, q) -> (q,): chain c adds the partials c, c + 64, .. in order from +0.0, then the tree over the chains"""
+    P, q = part.shape
+    rounds = -(-P // ROWS)
+    pad = np.zeros((rounds * ROWS, q))
+    pad[:P] = part
+    a = np.zeros((ROWS, q))
+    for t in range(rounds):
+        a = a + pad[t * ROWS:(t + 1) * ROWS]
+    return _tree(a.reshape(1, ROWS, q))[0]
+
+
+class _Rows:
+    """Row sums entry by entry in stored order: step j adds entry j of every row that has one."""
+
+    def __init__(self, indptr, indices, data):
+        self.n = len(indptr) - 1
+        length = np.diff(indptr)
+        order = np.argsort(-length, kind='stable')
+        self.steps = []
+        for j in range(int(length.max()) if self.n and len(indices) else 0):
+            rows = order[:int(np.count_nonzero(length > j))]
+            at = indptr[rows] + j
+            self.steps.append((rows, indices[at], data[at][:, None]))
+
+    def product(self, x):
+        s = np.zeros(x.shape)
+        for rows, cols, w in self.steps:
+            s[rows] = s[rows] + w * x[cols]
+        return s
+
+
+def _means(S1, Sc, sc, invn):
+    m = invn * S1
+    return m, invn * (Sc - sc * m)
+
+
+def ck_device_order(indptr, indices, data, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e-10, max_it=MAX_IT):
+    """(u, l, T, err history, capped).  The CSR arrays are W without its diagonal; val (m, k) the training rows' start values."""
+    indptr, indices, data = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64), np.asarray(data, dtype=np.float64)
+    n, k = len(indptr) - 1, val.shape[1]
+    rows = _Rows(indptr, indices, data)
+    d = rows.product(np.ones((n, 1)))          # sequential row sums from +0.0 (w * 1.0 is w)
+    c = np.zeros(n)
+    np.add.at(c, indices, data)                # unbuffered and in index order: rows ascending, a row's entries in stored order
+    sc = np.cumsum(c)[-1]                      # a sequential scan: c[0] + c[1] + ..
+    c = c[:, None]
+    invn = np.float64(1.0) / np.float64(n)
+    lab = np.full(n, -1, dtype=np.int64)
+    lab[np.asarray(ind, dtype=np.int64)] = np.arange(len(ind))
+    train = lab >= 0
+    with np.errstate(all='ignore'):
+        x = np.array(e, dtype=np.float64).reshape(n, 1)
+        nrm = np.float64(1.0)
+        m, yb = _means(*_finish(_partials(np.hstack([x, c * x]))), sc, invn)
+        l = np.float64(0.0)
+        for _ in range(power_it):
+            ev = x / nrm
+            w = (rows.product(ev) - d * m) - yb
+            S = _finish(_partials(np.hstack([ev * w, ev * ev, w * w, w, c * w])))
+            l = np.abs(S[0] / S[1])
+            nrm = np.sqrt(S[2])
+            m, yb = _means(S[3] / nrm, S[4] / nrm, sc, invn)
+            x = w
+        inva = np.float64(1.0) / (np.float64(alpha_frac) * l)
+        u = np.zeros((n, k))
+        u[train] = val[lab[train]]
+        S = _finish(_partials(np.hstack([u, c * u])))
+        m, yb = _means(S[:k], S[k:], sc, invn)
+        errs = []
+        err = np.float64(1.0)
+        while err > tol and len(errs) < max_it:
+            w = inva * ((rows.product(u) - d * m[None, :]) - yb[None, :]) - u
+            w[train] = 0.0
+            u = u + w
+            err = np.abs(w).view(np.uint64).max().view(np.float64)      # the maximum of the bit patterns: a NaN wins
+            errs.append(err)
+            S = _finish(_partials(np.hstack([u, c * u])))
+            m, yb = _means(S[:k], S[k:], sc, invn)
+    capped = bool(err > tol)
+    return np.ascontiguousarray(u), float(l), len(errs), np.array(errs, dtype=np.float64), capped
+
+
+def device_order_case(W, ind, labels, k, e, **kw):
+    """ck_device_order from what the learner is given: W with its diagonal, labels"""
+    Wd = without_diagonal(W)
+    val = np.ascontiguousarray(start_values(W.shape[0], ind, labels, k)[ind])
+    return ck_device_order(Wd.indptr, Wd.indices, Wd.data, ind, val, e, **kw)
+
+
+def predict(u):
+    """ssl.predict without class priors: argmax of the globally min/max-normalised scores (the first maximum wins)"""
+    s = u - np.min(u)
+    s = s / np.max(s)
+    return np.argmax(s, axis=1)
+
+
+def stop_tol(errs, T):
+    """A tol that makes iteration T the last one beyond doubt: halfway between err_T and the smallest err before it (err_0 = 1)"""
+    before = min(1.0, float(np.min(errs[:T - 1]))) if T > 1 else 1.0
+    assert errs[T - 1] < before, (T, errs[T - 1], before)
+    return 0.5 * (float(errs[T - 1]) + before)
+
+
+def top_two_gap(u, skip):
+    srt = np.sort(u, axis=1)
+    gap = srt[:, -1] - srt[:, -2] if u.shape[1] > 1 else np.full(len(u), np.inf)
+    keep = np.ones(len(u), dtype=bool)
+    keep[skip] = False
+    return float(gap[keep].min()) if keep.any() else np.inf
+
+
+# ---- seeded problems -----------------------------------------------------------------------------------------------------------------
+
+def random_problem(seed, n, k, hub=0, deg=6, directed=True, empty_rows=0, negative=0.1):
+    """(W without diagonal as canonical CSR, ind, val (m, k), e): a seeded random graph of about `deg` entries per row with weights, a share
+    `negative` of them below zero, `hub` > 0: row n // 2 stores exactly `hub` entries (n > hub), `empty_rows` rows store none."""
+    rng = np.random.default_rng(1800 + seed)
+    rows, cols = [], []
+    for i in range(n):
+        cnt = min(n - 1, int(rng.integers(1, 2 * deg)))
+        if hub and i == n // 2:
+            cnt = hub
+        if i < empty_rows and not (hub and i == n // 2):
+            cnt = 0
+        others = np.delete(np.arange(n), i)
+        cols.append(np.sort(rng.choice(others, size=cnt, replace=False)) if cnt else np.zeros(0, dtype=np.int64))
+        rows.append(np.full(cnt, i))
+    rows, cols = np.concatenate(rows).astype(np.int64), np.concatenate(cols).astype(np.int64)
+    data = rng.random(len(rows)) + 0.05
+    data[rng.random(len(rows)) < negative] *= -0.5
+    W = sparse.csr_matrix((data, (rows, cols)), shape=(n, n))
+    if not directed:
+        W = W + W.T
+    W = without_diagonal(W)
+    m = min(n, max(k, min(n // 3 + 1, 2 * k)))
+    ind = rng.choice(n, size=m, replace=False)
+    labels = np.arange(m) % k
+    val = np.ascontiguousarray(start_values(n, ind, labels, k)[ind]) if k > 1 else rng.normal(size=(m, 1))      # (one class centres to zero)
+    e = rng.random(n)
+    return W, ind.astype(np.int64), val, e
+
+
+# ---- csrc/ck_plan.h on the host ------------------------------------------------------------------------------------------------------
+
+def build_host_lib(tmp):
+    """csrc/ck_plan.h compiled for the host: `g++ -O2 -ffp-contract=off` behind tests/ck_plan_host.cpp."""
+    so = os.path.join(str(tmp), 'libck_plan_host.so')
+    subprocess.run(['g++', '-O2', '-ffp-contract=off', '-std=c++17', '-fPIC', '-shared', '-I' + os.path.join(ROOT, 'graphlearning_amd', 'csrc'),
+                    '-o', so, os.path.join(ROOT, 'tests', 'ck_plan_host.cpp')], check=True)
+    lib = ctypes.CDLL(so)
+    vp, i64, f64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
+    lib.ck_host_validate.argtypes = [i64, i64, vp, vp, vp, ctypes.c_int, i64, vp, i64, f64, i64]
+    lib.ck_host_validate.restype = ctypes.c_int
+    lib.ck_host_solve.argtypes = [i64, i64, vp, vp, vp, ctypes.c_int, i64, vp, vp, vp, i64, f64, f64, i64, ctypes.c_int, vp, vp, vp, vp, i64]
+    lib.ck_host_solve.restype = ctypes.c_int
+    lib.ck_host_tiles.argtypes = [ctypes.c_int, vp, ctypes.c_int]
+    lib.ck_host_tiles.restype = ctypes.c_int
+    return lib
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def host_validate(lib, indptr, indices, data, k, ind, power_it=100, alpha_frac=1.05, max_it=MAX_IT):
+    indptr, indices = np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32)
+    data, ind = np.ascontiguousarray(data, dtype=np.float64), np.ascontiguousarray(ind, dtype=np.int32)
+    return lib.ck_host_validate(len(indptr) - 1, len(indices), _p(indptr), _p(indices), _p(data), k, len(ind), _p(ind), power_it, alpha_frac, max_it)
+
+
+def host_solve(lib, indptr, indices, data, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e-10, max_it=MAX_IT, chunk=64, cap=0):
+    """ck_host_reference with this chunk length: (u, l, T, err history[:min(T, cap)], capped); ValueError if ck_validate refuses"""
+    indptr, indices = np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32)
+    data, ind = np.ascontiguousarray(data, dtype=np.float64), np.ascontiguousarray(ind, dtype=np.int32)
+    val, e = np.ascontiguousarray(val, dtype=np.float64), np.ascontiguousarray(e, dtype=np.float64).ravel()
+    n, k = len(indptr) - 1, val.shape[1]
+    u = np.empty((n, k))
+    l, T = np.zeros(1), np.zeros(1, dtype=np.int64)
+    hist = np.full(cap, np.nan)
+    rc = lib.ck_host_solve(n, len(indices), _p(indptr), _p(indices), _p(data), k, len(ind), _p(ind), _p(val), _p(e), power_it, alpha_frac, tol,
+                           max_it, chunk, _p(u), _p(l), _p(T), _p(hist), cap)
+    if rc < 0:
+        raise ValueError('ck_validate refused the arrays: %d' % -rc)
+    return u, float(l[0]), int(T[0]), hist[:min(int(T[0]), cap)], rc == 1
+
+
+def host_tiles(lib, k):
+    out = np.zeros(2 * 32, dtype=np.int32)
+    nt = lib.ck_host_tiles(k, _p(out), 32)
+    return out[:2 * nt].reshape(nt, 2)
