@@ -301,7 +301,7 @@ struct KnnPass {
       GLX_POOL(glx_pool_alloc((void**)&b.Rf, (size_t)n * p.dpa * 4));
       GLX_POOL(glx_pool_alloc((void**)&b.Qf, (size_t)n * p.dpa * 4));
       hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean,
-                         n, d, p.dpa, b.Rf, b.Qf, b.qnorm);
+                         (const float*)b.rmax, n, d, p.dpa, b.Rf, b.Qf, b.qnorm);
       GLX_HIP(hipGetLastError());
       return GLX_OK;
     }
@@ -310,10 +310,10 @@ struct KnnPass {
     if (p.cat) {
       GLX_POOL(glx_pool_alloc((void**)&b.Xq, (size_t)(n + KNN_PAD_ROWS) * 64 * 2));
       hipLaunchKernelGGL(knn_prep_bf16_cat_kernel, dim3((unsigned)((n + KNN_PAD_ROWS + 255) / 256)), dim3(256), 0, st, (const double*)b.X,
-                         (const double*)b.mean, n, d, b.Xb, b.Xq, b.nrm, b.qnorm, p.cat == 2 ? 1 : 0);
+                         (const double*)b.mean, (const float*)b.rmax, n, d, b.Xb, b.Xq, b.nrm, b.qnorm, p.cat == 2 ? 1 : 0);
     } else {
       hipLaunchKernelGGL(knn_prep_bf16_kernel, dim3((unsigned)((n + KNN_PAD_ROWS + 255) / 256)), dim3(256), 0, st, (const double*)b.X, (const double*)b.mean,
-                         n, d, p.dpa, b.Xb, b.nrm, b.qnorm);
+                         (const float*)b.rmax, n, d, p.dpa, b.Xb, b.nrm, b.qnorm);
     }
     GLX_HIP(hipGetLastError());
     const KnnSeedPlan seed = knn_seed_plan(p, k, cell_starts ? ncells : 0);

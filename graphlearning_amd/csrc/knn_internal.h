@@ -41,7 +41,8 @@ struct KnnBufs {
   unsigned short* Xq = nullptr;      // concatenated form only: the query image [hi | lo | hi]
   float* nrm = nullptr;              // fp32 squared norms (bf16 filter)
   double* part = nullptr;            // per-block partial column sums / maxima of the centring pass
-  float* rmax = nullptr;             // [0] largest centred norm (1 + 1e-6), [1] 1 if the input is finite: written by knn_rmax_kernel
+  float* rmax = nullptr;             // [0] largest centred norm of the SCALED operands (1 + 1e-6), [1] 1 if the input is finite, bytes 8 .. 15: the
+                                     // scale (a double, knn_filter_scale): written by knn_rmax_kernel, read through knn_scale_of
   double *X = nullptr, *mean = nullptr, *dist = nullptr;
   float *Rf = nullptr, *Qf = nullptr, *qnorm = nullptr, *cand_d = nullptr;
   float* pre_d = nullptr;
@@ -87,12 +88,14 @@ struct KnnBufs {
 };
 
 // ---- knn_prep.hip ------------------------------------------------------------------------------------------------------
-__global__ void knn_prep_kernel(const double* __restrict__ X, const double* __restrict__ mean, int64_t n, int d, int dpa,
-                                float* __restrict__ Rf, float* __restrict__ Qf, float* __restrict__ qnorm);
-__global__ void knn_prep_bf16_kernel(const double* __restrict__ X, const double* __restrict__ mean, int64_t n, int d, int kpad,
-                                     unsigned short* __restrict__ Xb, float* __restrict__ nrm, float* __restrict__ qnorm);
-__global__ void knn_prep_bf16_cat_kernel(const double* __restrict__ X, const double* __restrict__ mean, int64_t n, int d,
-                                         unsigned short* __restrict__ Xa, unsigned short* __restrict__ Xq, float* __restrict__ nrm,
+// the exact power of two the filter's operands were multiplied by (knn_plan.h: knn_filter_scale; 1 for data inside the window)
+__device__ __forceinline__ double knn_scale_of(const float* __restrict__ rmax_p) { return ((const double*)rmax_p)[1]; }
+__global__ void knn_prep_kernel(const double* __restrict__ X, const double* __restrict__ mean, const float* __restrict__ rmax_p, int64_t n, int d,
+                                int dpa, float* __restrict__ Rf, float* __restrict__ Qf, float* __restrict__ qnorm);
+__global__ void knn_prep_bf16_kernel(const double* __restrict__ X, const double* __restrict__ mean, const float* __restrict__ rmax_p, int64_t n,
+                                     int d, int kpad, unsigned short* __restrict__ Xb, float* __restrict__ nrm, float* __restrict__ qnorm);
+__global__ void knn_prep_bf16_cat_kernel(const double* __restrict__ X, const double* __restrict__ mean, const float* __restrict__ rmax_p, int64_t n,
+                                         int d, unsigned short* __restrict__ Xa, unsigned short* __restrict__ Xq, float* __restrict__ nrm,
                                          float* __restrict__ qnorm, int fold);
 __global__ __launch_bounds__(256) void knn_colsum_kernel(const double* __restrict__ X, int64_t n, int d, int dt, double* __restrict__ part);
 __global__ __launch_bounds__(256) void knn_mean_kernel(const double* __restrict__ part, int64_t nblk, int d, int64_t n, double* __restrict__ mean);

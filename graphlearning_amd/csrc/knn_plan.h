@@ -19,6 +19,43 @@ static const int KNN_K_NARROW = 60;    // neighbours (self included) of the list
 static const int KNN_K_MAX = 1024;     // neighbours (self included) of the wide search (glx_knn_search)
 static const size_t KNN_CAND_BUDGET = (size_t)1 << 30;   // bytes of candidates (value + index) a wide pass holds at once: its query chunks
 
+// ---- the scale of the filter's operands ------------------------------------------------------------------------------------------
+// The filter's error bound (cerr, below) is RELATIVE: |filter value - exact dist^2| <= cerr (|q| + rmax)^2 holds while every fp32
+// product and sum of the centred operands is a normal number, i.e. loses a relative 2^-24 and not an absolute 2^-149 (or everything:
+// overflow).  With rmax the largest centred norm and coordinates c <= rmax:
+//   below: a product or a split piece under 2^-126 carries an absolute error <= 2^-126 (flushed altogether at worst); there are
+//          3 dpa + 8 products and sums and 2 d pieces per value (d <= 16382), in total U <= 2^-126 (4 sqrt(d) rmax + 2 (3 dpa + 8) + 2 d)
+//          <= 2^-108, against a bound of at least cerr rmax^2 >= 2^-16 rmax^2: U is 2^-12 of the bound at rmax = 2^-40;
+//   above: filter values reach 4 rmax^2 = 2^82 at rmax = 2^40, far below the 1e30 at which the spare rows behind the data count
+//          as infinitely far, and below fp32's 2^128.
+// So the bound is valid for KNN_RMAX_LO <= rmax <= KNN_RMAX_HI, and data inside that window is taken as it comes (every list,
+// count and statistic of such data is what it was before the window existed).  Outside it the centred operands are multiplied,
+// in fp64 and before they are rounded to fp32, by the exact power of two that brings rmax into [1, 2) (knn_rmax_kernel decides,
+// on the device; the prep kernels apply it): the filter then works in units of 1 / scale.  Everything in those units stays in
+// them -- the norms, rmax itself, eps, the lists' thresholds, the seed --; the two places where a filter value meets an exact fp64
+// distance convert: the acceptance test of the re-rank compares with dk2 scale^2, and the seeding pre-pass hands the cell pruning
+// ub2 / scale^2.  Measured before the scaling existed (tests/test_gpu_knn_scale.py): wrong lists at data scaled by 2^-72 .. 2^-80
+// (values that are multiples of 2^-149 passed the acceptance test) and by 2^+55 (norms of some rows overflow to inf, those refs
+// enter no list, and a list that is not full does not count against a row).
+// rmax = 0, not finite, or below fp64's normal range: no scaling (nothing would make the filter sharp; the host refuses non-finite
+// input, and where the centred norms are subnormal in fp64 the exact distances themselves underflow).
+#if defined(__HIPCC__)
+#define KNN_HOST_DEVICE __host__ __device__
+#else
+#define KNN_HOST_DEVICE
+#endif
+constexpr double KNN_RMAX_LO = 0x1p-40, KNN_RMAX_HI = 0x1p+40;
+KNN_HOST_DEVICE inline double knn_filter_scale(double rmax) {
+  if (rmax >= KNN_RMAX_LO && rmax <= KNN_RMAX_HI) return 1.0;
+  if (!(rmax >= 0x1p-1022 && rmax < 0x1p+1023)) return 1.0;    // 0, subnormal, inf, NaN (and the last binade, whose 2^-E is subnormal)
+  uint64_t bits;
+  __builtin_memcpy(&bits, &rmax, 8);
+  bits = (uint64_t)(2046 - ((bits >> 52) & 0x7ff)) << 52;      // 2^-E for rmax = m 2^E, 1 <= m < 2 (E in [-1022, 1022]: a normal number)
+  double scale;
+  __builtin_memcpy(&scale, &bits, 8);
+  return scale;
+}
+
 // features per half per block of the blocked (d > 130) fp32 variant; 16 where the KP = 64 lists leave less LDS
 constexpr int knn_kb(int KP) { return KP == 64 ? 16 : 32; }   // (KP = 8 never takes the blocked variant)
 
@@ -54,7 +91,7 @@ struct KnnPlan {
   int64_t chunk, nchunks;   // queries whose candidates are held at once (wide: within KNN_CAND_BUDGET), passes over them
   bool short_lists, wide, use_bf16;
   int cat;              // bf16 filter: 0 blocks of 16 features, 1 concatenated operands, 2 with the norm folded in
-  double cerr;          // |filter value - exact dist^2| <= cerr * (|q| + rmax)^2
+  double cerr;          // |filter value - exact dist^2| <= cerr * (|q| + rmax)^2, for operands scaled by knn_filter_scale(rmax)
 };
 
 inline KnnPlan knn_make_plan(int64_t n, int d, int k, int64_t nq, bool long_lists, const glx_knn_options& opt) {
@@ -124,12 +161,13 @@ inline KnnPlan knn_make_plan(int64_t n, int d, int k, int64_t nq, bool long_list
   // candidates otherwise, 33 GB at 10^6; the lists of k <= 60 are short enough to be held for all queries at once
   const int64_t chunk = wide ? std::min<int64_t>(nq, std::max<int64_t>(BQ, (int64_t)((KNN_CAND_BUDGET / ((size_t)ncand * 8)) / BQ * BQ))) : nq;
   const int64_t nchunks = (nq + chunk - 1) / chunk;
-  // |filter value - exact dist^2| <= cerr * (|q| + rmax)^2.
+  // |filter value - exact dist^2| <= cerr * (|q| + rmax)^2, valid for KNN_RMAX_LO <= rmax <= KNN_RMAX_HI (above: the products and sums
+  // of the bound's derivation are normal fp32 numbers there); knn_filter_scale brings every other input into that range.
   // fp32 filter: input rounding (2^-24 per coordinate), dpa products and sums at 2^-24 each, norms computed in fp32; generous constant.
   // bf16 filter: eps = cerr (|q| + rmax)^2 with cerr ~ 2^-16.  The dropped parts of the split products (lo.lo and the residuals of the
   // two roundings) are <= 3.1 * 2^-16 |q||r| in q.r in the worst case -- every coordinate's errors at their bounds and aligned --, twice
   // that in the distance, i.e. <= 1.55 * 2^-16 (|q| + rmax)^2; plus 3 kpad fp32 accumulations, fp32 norms and input rounding (the second
-  // term, doubled: the matrix pipe's internal rounding mode is not documented).  So |filter - exact| < 2 eps ALWAYS, which is what the
+  // term, doubled: the matrix pipe's internal rounding mode is not documented).  So |filter - exact| < 2 eps within that range, which is what the
   // acceptance test of the re-rank needs (it asks for a margin of 2 eps), and <= 0.52 eps on every pair of the randomised suite's inputs
   // (an emulation of the split arithmetic: profiles/r05_knn_tile_pmc.txt); the re-rank's fp32 screen allows for 2 eps per value as well.
   const double cerr = use_bf16 ? 2.0 * (std::ldexp(1.0, -17) + (1.5 * (3.0 * dpa + 4.0) + d + 16.0) * std::ldexp(1.0, -24))

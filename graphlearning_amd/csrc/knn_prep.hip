@@ -5,13 +5,15 @@
 
 // ---- stage 0: centred fp32 images with the norms folded in ---------------------------------
 // Rf[i] = [x_0..x_{d-1}, 0.., |x|^2, 1]   Qf[i] = [-2x_0..-2x_{d-1}, 0.., 1, |x|^2]   (dpa floats)
-__global__ void knn_prep_kernel(const double* __restrict__ X, const double* __restrict__ mean, int64_t n, int d, int dpa,
-                                float* __restrict__ Rf, float* __restrict__ Qf, float* __restrict__ qnorm) {
+// (all three prep kernels: the centred value times the scale of knn_filter_scale -- exact, in fp64 -- is what gets rounded to fp32)
+__global__ void knn_prep_kernel(const double* __restrict__ X, const double* __restrict__ mean, const float* __restrict__ rmax_p, int64_t n, int d,
+                                int dpa, float* __restrict__ Rf, float* __restrict__ Qf, float* __restrict__ qnorm) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const double sc = knn_scale_of(rmax_p);
   float nrm = 0.f;
   for (int f = 0; f < d; ++f) {
-    const float x = (float)(X[i * d + f] - mean[f]);
+    const float x = (float)((X[i * d + f] - mean[f]) * sc);
     Rf[i * dpa + f] = x;
     Qf[i * dpa + f] = -2.f * x;
     nrm = fmaf(x, x, nrm);
@@ -32,8 +34,8 @@ __device__ __forceinline__ unsigned short f32_to_bf16_rn(float x) {
 __device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 
 // Xb[i] = [hi_0 .. hi_{kpad-1} | lo_0 .. lo_{kpad-1}] (bf16), nrm[i] = |x32|^2 (fp32), qnorm[i] = |x32|
-__global__ void knn_prep_bf16_kernel(const double* __restrict__ X, const double* __restrict__ mean, int64_t n, int d, int kpad,
-                                     unsigned short* __restrict__ Xb, float* __restrict__ nrm, float* __restrict__ qnorm) {
+__global__ void knn_prep_bf16_kernel(const double* __restrict__ X, const double* __restrict__ mean, const float* __restrict__ rmax_p, int64_t n,
+                                     int d, int kpad, unsigned short* __restrict__ Xb, float* __restrict__ nrm, float* __restrict__ qnorm) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n + KNN_PAD_ROWS) return;
   // (eight features at a time: their hi and lo halves leave in one 16-byte store each -- two-byte stores made this kernel 2.3 ms at
@@ -46,6 +48,7 @@ __global__ void knn_prep_bf16_kernel(const double* __restrict__ X, const double*
     nrm[i] = 1e30f;
     return;
   }
+  const double sc = knn_scale_of(rmax_p);
   float s = 0.f;
   for (int u = 0; u < kpad / 8; ++u) {
     unsigned short hi[8], lo[8];
@@ -54,7 +57,7 @@ __global__ void knn_prep_bf16_kernel(const double* __restrict__ X, const double*
       const int f = u * 8 + e;
       hi[e] = 0; lo[e] = 0;
       if (f < d) {
-        const float x = (float)(X[i * d + f] - mean[f]);
+        const float x = (float)((X[i * d + f] - mean[f]) * sc);
         hi[e] = f32_to_bf16_rn(x);
         lo[e] = f32_to_bf16_rn(x - bf16_to_f32(hi[e]));
         s = fmaf(x, x, s);
@@ -76,8 +79,8 @@ __global__ void knn_prep_bf16_kernel(const double* __restrict__ X, const double*
 // fold (d <= 20: the slots 20, 41, 62 of the three segments are free): the ref image holds -2 x (exact) and, in the free slots,
 // |x|^2 as three bf16 pieces against ones in the query image -- the contraction then IS the selection value |r|^2 - 2 q.r and the
 // tile kernel needs neither the norms of the tile nor an fma per pair (measured by ablation: 11 % of the config-2 tile kernel)
-__global__ void knn_prep_bf16_cat_kernel(const double* __restrict__ X, const double* __restrict__ mean, int64_t n, int d,
-                                         unsigned short* __restrict__ Xa, unsigned short* __restrict__ Xq, float* __restrict__ nrm,
+__global__ void knn_prep_bf16_cat_kernel(const double* __restrict__ X, const double* __restrict__ mean, const float* __restrict__ rmax_p, int64_t n,
+                                         int d, unsigned short* __restrict__ Xa, unsigned short* __restrict__ Xq, float* __restrict__ nrm,
                                          float* __restrict__ qnorm, int fold) {
   // (a row of each image is put together in registers and leaves in eight 16-byte stores: 128 two-byte stores per row and image
   // took 78 us at 70 000 rows)
@@ -92,10 +95,11 @@ __global__ void knn_prep_bf16_cat_kernel(const double* __restrict__ X, const dou
   } else {
     float s = 0.f;
     const float sc = fold ? -2.f : 1.f;
+    const double fsc = knn_scale_of(rmax_p);
 #pragma unroll
     for (int f = 0; f < KNN_CAT_SEG; ++f) {
       if (f < d) {
-        const float x = (float)(X[i * d + f] - mean[f]);
+        const float x = (float)((X[i * d + f] - mean[f]) * fsc);
         const unsigned short hi = f32_to_bf16_rn(x);
         const unsigned short lo = f32_to_bf16_rn(x - bf16_to_f32(hi));
         const unsigned short shi = f32_to_bf16_rn(sc * bf16_to_f32(hi)), slo = f32_to_bf16_rn(sc * bf16_to_f32(lo));   // (exact: a power of two)
@@ -217,7 +221,8 @@ __global__ __launch_bounds__(256) void knn_maxnorm_kernel(const double* __restri
   }
   if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
 }
-// rmax_out[0] = sqrt(max) * (1 + 1e-6) as a float (what the re-rank's acceptance bound uses), [1] = 1 if the input is finite
+// rmax_out[0] = sqrt(max) * scale * (1 + 1e-6) as a float (what the re-rank's acceptance bound uses: the largest norm of the operands as
+// the prep kernels scale them), [1] = 1 if the input is finite, bytes 8 .. 15 = the scale as a double (knn_plan.h: knn_filter_scale)
 __global__ __launch_bounds__(256) void knn_rmax_kernel(const double* __restrict__ part, int64_t nblk, float* __restrict__ rmax_out) {
   double m = 0.0;
   for (int64_t b = threadIdx.x; b < nblk; b += 256) m = part[b] > m ? part[b] : m;
@@ -230,8 +235,10 @@ __global__ __launch_bounds__(256) void knn_rmax_kernel(const double* __restrict_
   }
   if (threadIdx.x == 0) {
     const double r2 = sm[0];
-    rmax_out[0] = (float)(sqrt(r2) * (1.0 + 1e-6));
+    const double r = sqrt(r2), sc = knn_filter_scale(r);
+    rmax_out[0] = (float)(r * sc * (1.0 + 1e-6));
     rmax_out[1] = (r2 == r2 && r2 < INFINITY) ? 1.0f : 0.0f;
+    ((double*)rmax_out)[1] = sc;
   }
 }
 
@@ -285,7 +292,10 @@ __global__ __launch_bounds__(256) void knn_seed_kernel(const float* __restrict__
     seed = nextafterf(seed, INFINITY);
     key = __float_as_int(seed);
     key ^= (key >> 31) & 0x7fffffff;
-    if (ub2) ub2[ql] = (double)vk + eps;        // exact k-th distance^2 <= this
+    if (ub2) {                                  // exact k-th distance^2 <= this, in the data's own units (the cell pruning compares it with fp64 distances)
+      const double unscale = 1.0 / knn_scale_of(rmax_p);     // (exact: a power of two; twice, since its square may leave fp64's range)
+      ub2[ql] = ((double)vk + eps) * unscale * unscale;
+    }
   } else if (ub2) {
     ub2[ql] = INFINITY;
   }

@@ -174,11 +174,14 @@ __global__ __launch_bounds__(64) void knn_rerank_kernel(const double* __restrict
   // every ref outside a full list has fp32 dist^2 >= that list's threshold; accept the row only if no such ref can beat the exact
   // k-th neighbour once the fp32 error is allowed for.  One lane per list (the lists' thresholds = their largest entries: they
   // arrive unsorted; INFINITY while a list is not full)
+  // (tau and eps0 are in the filter's units, dk2 is exact and in the data's: knn_plan.h, knn_filter_scale; the scale is applied twice
+  // since its square may leave fp64's range)
+  const double fsc = knn_scale_of(rmax_p), dk2s = dk2 * fsc * fsc;
   int bad = 0;
   for (int l = lane; l < lists; l += 64) {
     float tau = 0.f;
     for (int p = 0; p < KP; ++p) tau = fmaxf(tau, cand_d[ql * ncand + l * KP + p]);
-    if (tau < INFINITY && !((double)tau >= dk2 + 2.0 * eps0)) bad = 1;
+    if (tau < INFINITY && !((double)tau >= dk2s + 2.0 * eps0)) bad = 1;
   }
   bad = __any(bad) || !(dk2 < INFINITY);
   if (lane == 0) {
@@ -559,11 +562,12 @@ __global__ __launch_bounds__(256) void knn_rerank_wide_kernel(const double* __re
     dist_out[orow * k + c] = sqrt(sd[c]);
   }
   const double dk2 = sd[k - 1];
+  const double fsc = knn_scale_of(rmax_p), dk2s = dk2 * fsc * fsc;       // (the filter's units, as in knn_rerank_kernel)
   int bad = 0;
   for (int l = tid; l < lists; l += 256) {
     float tau = 0.f;
     for (int p = 0; p < KP; ++p) tau = fmaxf(tau, cd[l * KP + p]);
-    if (tau < INFINITY && !((double)tau >= dk2 + 2.0 * eps0)) bad = 1;
+    if (tau < INFINITY && !((double)tau >= dk2s + 2.0 * eps0)) bad = 1;
   }
   bad = __syncthreads_or(bad) || !(dk2 < INFINITY);
   if (tid == 0) {

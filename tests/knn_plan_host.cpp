@@ -3,6 +3,7 @@
 //   extras           the later decisions: S rows (seeding), E rows (escalation: the smallest count of flagged rows that escalates,
 //                    and the decision either side of it and of 64 | 65), F rows (the wide fallback's sizes)
 //   chain FILE M D   knn_chain_places of the M x D doubles in FILE: the places, one line
+//   scale R ...      knn_filter_scale of every R (hex floats welcome): one "%a" per line
 // The row formats are those of the table recorded in tests/golden/knn_plans.txt.
 #include "knn_plan.h"
 #include <cstdio>
@@ -104,6 +105,10 @@ int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "plans")) { plans(); return 0; }
   if (argc == 2 && !strcmp(argv[1], "extras")) { extras(); return 0; }
   if (argc == 5 && !strcmp(argv[1], "chain")) return chain(argv[2], atoi(argv[3]), atoi(argv[4]));
-  fprintf(stderr, "usage: knn_plan_host plans | extras | chain FILE M D\n");
+  if (argc >= 3 && !strcmp(argv[1], "scale")) {
+    for (int a = 2; a < argc; ++a) printf("%a\n", knn_filter_scale(strtod(argv[a], nullptr)));
+    return 0;
+  }
+  fprintf(stderr, "usage: knn_plan_host plans | extras | chain FILE M D | scale R ...\n");
   return 2;
 }

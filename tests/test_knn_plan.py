@@ -1,5 +1,6 @@
 """graphlearning_amd/csrc/knn_plan.h, the plan of one pass of the exact kNN search (list length, tile width, ref ranges, candidate
-count, query chunks, the filter's error constant, the seeding / escalation / wide-fallback decisions) and the chain of the cells:
+count, query chunks, the filter's error constant, the seeding / escalation / wide-fallback decisions), the power of two the filter's
+operands are scaled by and the chain of the cells:
 built on the host with no HIP header (tests/knn_plan_host.cpp) and compared with the table recorded from the search pass as it
 stood before the plan was a header of its own (tests/golden/knn_plans.txt)."""
 import hashlib
@@ -160,3 +161,21 @@ def test_chain_of_the_cells(driver, m, d):
     got = np.array(driver('chain', path, m, d).split(), dtype=np.int64)
     assert np.array_equal(np.sort(got), np.arange(m))
     assert np.array_equal(got, chain_places(cen))
+
+
+def test_scale_of_the_filters_operands(driver):
+    """knn_filter_scale: 1 inside the window [2^-40, 2^40] in which the filter's relative error bound is valid (data there is taken
+    as it comes), elsewhere the exact power of two that brings the largest centred norm into [1, 2); 1 where nothing can be done."""
+    def scales(values):
+        return [float.fromhex(t) for t in driver('scale', *[v.hex() for v in values]).split()]
+    inside = [2.0 ** -40, 2.0 ** -40 * (1 + 2.0 ** -52), 1e-6, 1.0, 1.5, 1e6, 2.0 ** 40 * (1 - 2.0 ** -53), 2.0 ** 40]
+    assert scales(inside) == [1.0] * len(inside)
+    rng = np.random.default_rng(5)
+    outside = [2.0 ** -40 * (1 - 2.0 ** -53), 2.0 ** 40 * (1 + 2.0 ** -52), 1e-20, 1e20, 2.0 ** -1022, 2.0 ** 1023 * (1 - 2.0 ** -53), 2.0 ** -66 * 1024,
+               2.0 ** 400 * 1447.3] + list(np.ldexp(rng.uniform(1, 2, 64), rng.integers(-1022, -41, 64))) + list(np.ldexp(rng.uniform(1, 2, 64), rng.integers(41, 1023, 64)))
+    for r, s in zip(outside, scales(outside)):
+        m, e = np.frexp(s)
+        assert m == 0.5 and 1.0 <= r * s < 2.0, (r, s)                 # an exact power of two, a normal number; r * s is exact
+        assert np.isfinite(s) and s >= 2.0 ** -1022
+    nothing = [0.0, 5e-324, 2.0 ** -1023, 2.0 ** 1023, float('inf'), float('nan')]
+    assert scales(nothing) == [1.0] * len(nothing)
