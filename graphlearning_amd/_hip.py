@@ -161,6 +161,13 @@ _SIGNATURES = {
                              C.c_int],
     'glx_ck_solve': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp,
                      _f64p, _i64p, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
+    'glx_eig_create': [C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
+    'glx_eig_set_column': [_vp, C.c_int, _vp],
+    'glx_eig_orthonormalize': [_vp, C.c_int, _f64p],
+    'glx_eig_run': [_vp, C.c_int, C.c_int, _vp, _vp],
+    'glx_eig_rotate': [_vp, _vp, C.c_int, C.c_int],
+    'glx_eig_get_columns': [_vp, C.c_int, C.c_int, _vp],
+    'glx_eig_destroy': [_vp],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1225,6 +1232,73 @@ def ck_solve(row_ptr, col, W, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e
 
 
 _CK_ITERATE_FN = C.CFUNCTYPE(C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_double, _vp)
+
+
+class Eig:
+    """The device half of the thick-restart Lanczos eigensolver (glx_eig_*, csrc/eig.hip; the contract is DESIGN.md 4.12): a
+    symmetric matrix A as canonical CSR arrays (row_ptr, col, val) and a basis of m + 1 column-major Lanczos vectors that stays on
+    the device.  The backend interface of graphlearning_amd._eig.thick_restart: set_column, orthonormalize, run, rotate,
+    get_columns.  A context manager; close() releases the device memory.  GlxError on every refusal of the library."""
+
+    def __init__(self, row_ptr, col, val, m, device=None):
+        self._h = _vp()
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        n = len(row_ptr) - 1
+        if row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or val.shape != col.shape or (n >= 1 and int(row_ptr[-1]) != len(col)):
+            raise GlxError('Eig: inconsistent array shapes or sizes')
+        self.n, self.m = n, int(m)
+        check(load().glx_eig_create(n, _ptr(row_ptr), _ptr(col), _ptr(val), int(m), _dev(device), C.byref(self._h)), 'glx_eig_create')
+
+    def _handle(self):
+        if not self._h.value:
+            raise GlxError('Eig: the object is closed')
+        return self._h
+
+    def set_column(self, j, x):
+        x = _dense(np.asarray(x).ravel(), np.float64, (self.n,), 'column')
+        check(load().glx_eig_set_column(self._handle(), int(j), _ptr(x)), 'glx_eig_set_column')
+
+    def orthonormalize(self, j):
+        norm = C.c_double(0.0)
+        check(load().glx_eig_orthonormalize(self._handle(), int(j), C.byref(norm)), 'glx_eig_orthonormalize')
+        return float(norm.value)
+
+    def run(self, j0, j1):
+        count = max(int(j1) - int(j0), 1)
+        alpha, beta = np.empty(count), np.empty(count)
+        check(load().glx_eig_run(self._handle(), int(j0), int(j1), _ptr(alpha), _ptr(beta)), 'glx_eig_run')
+        return alpha, beta
+
+    def rotate(self, Y, rows, keep):
+        Y = _dense(Y, np.float64, (int(rows), int(keep)), 'Y')
+        check(load().glx_eig_rotate(self._handle(), _ptr(Y), int(rows), int(keep)), 'glx_eig_rotate')
+
+    def get_columns(self, j0, j1):
+        """(n, j1 - j0): the columns j0 .. j1 - 1 of the basis"""
+        out = np.empty((max(int(j1) - int(j0), 1), self.n))
+        check(load().glx_eig_get_columns(self._handle(), int(j0), int(j1), _ptr(out)), 'glx_eig_get_columns')
+        return np.ascontiguousarray(out.T)
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            lib = load(required=False)
+            if lib is not None:
+                lib.glx_eig_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def host_row_sums(W):

@@ -24,6 +24,10 @@ class graph:
         self.num_nodes = W.shape[0]
         self.label_names = label_names
         self.node_names = node_names
+        # what eigen_decomp computed last, per normalization (reference graph.py:55-67)
+        self.eigendata = {norm: dict.fromkeys(('eigenvectors', 'eigenvalues', 'method', 'k', 'c', 'gamma', 'tol', 'q'))
+                          for norm in ('combinatorial', 'randomwalk', 'normalized')}
+        self.eig_steps = self.eig_restarts = self.eig_probe = None
 
     def degree_vector(self):
         """d_i = sum_j w_ij (row sums; reference graph.py:108-122)."""
@@ -48,6 +52,58 @@ class graph:
         else:
             sys.exit('Invalid option for graph Laplacian normalization.')
         return L.tocsr()
+
+    def eigen_decomp(self, normalization='combinatorial', method='exact', k=10, c=None, gamma=0, tol=0, q=1, device=None):
+        """The k lowest eigenvalues (ascending) and eigenvectors (n, k) of the combinatorial, random-walk or normalised graph
+        Laplacian (reference graph.py:623-850, method='exact', gamma=0), cached in self.eigendata[normalization] under the reference's
+        six parameters.  The reference takes `svds` (ARPACK) of A = D^-1/2 W D^-1/2, or of M I - L with M = 2 max(deg), and returns
+        1 - s or M - s; here the k largest singular values of the same A, built on the host by the same scipy expressions, come from
+        thick-restart Lanczos with full reorthogonalisation on A A on the GPU (csrc/eig.hip, _eig.py).  `tol` is the
+        relative residual at which a Ritz pair counts as converged, 0 = machine precision as in ARPACK.  The vectors are the
+        eigenvectors v of A A (scipy's u = A v / s is +-v for a symmetric A), times D^-1/2 for 'randomwalk' as in the reference;
+        their signs are arbitrary, as the reference's are.  Sets eig_steps (Lanczos steps), eig_restarts and eig_probe.
+
+        The result is held to a TOLERANCE contract against the reference (eigenvalues, invariant subspace, residual: the bounds
+        measured in tests/golden/g19_eig.npz), and to a bit-for-bit contract against the host restatement of csrc/eig_plan.h.
+
+        Stated deviations, each a ValueError before any device call: a W that is not symmetric bit for bit, a vertex of degree 0 for
+        the two normalised forms, NaN / infinite / negative weights, k < 1, k >= n, k > 256.  NotImplementedError: method='lowrank'
+        (randomised SVD) and gamma != 0 (modularity).  GlxError at run time: a breakdown (fewer reachable distinct eigenvalues than
+        basis columns, e.g. a complete graph), and a missed multiple eigenvalue -- a single-vector Krylov method finds one vector per
+        distinct eigenvalue, so after convergence a second random vector probes the complement for a few steps; disconnected and
+        bipartite graphs usually end there.  The probe detects, it does not prove absence, and nothing is repaired."""
+        from . import _hip, _eig
+        if c is None:
+            c = 2 * k
+        if normalization not in self.eigendata:
+            sys.exit('Invalid choice of normalization')
+        data = self.eigendata[normalization]
+        params = {'method': method, 'k': k, 'c': c, 'gamma': gamma, 'tol': tol, 'q': q}
+        if data['eigenvalues'] is not None and all(data[name] == value for name, value in params.items()):
+            return data['eigenvalues'], data['eigenvectors']
+        if method == 'lowrank':
+            raise NotImplementedError("eigen_decomp(method='lowrank') is randomised SVD, which this package does not provide")
+        if method != 'exact':
+            sys.exit('Invalid eigensolver method ' + method)
+        if gamma != 0:
+            raise NotImplementedError('eigen_decomp(gamma != 0) needs an eigensolver on an operator with a rank-one term '
+                                      '(modularity), which this package does not provide')
+        k = int(k)
+        _eig.check_weights(self.weight_matrix, normalization, k)
+        A, D, M = _eig.operator(self.weight_matrix, normalization)
+        n = self.num_nodes
+        with _hip.Eig(A.indptr, A.indices, A.data, _eig.basis_size(n, k), device=device) as backend:
+            theta, self.eig_steps, self.eig_restarts, self.eig_probe = _eig.thick_restart(backend, n, k, tol=tol)
+            vecs = backend.get_columns(0, k)
+        s = np.sqrt(np.maximum(theta, 0.0))
+        vals = (1 - s) if M is None else (M - s)
+        ind = np.argsort(vals, kind='stable')
+        vals, vecs = vals[ind], vecs[:, ind]
+        if normalization == 'randomwalk':
+            vecs = D @ vecs
+        data.update(params)
+        data['eigenvalues'], data['eigenvectors'] = vals, vecs
+        return vals, vecs
 
     def reweight(self, idx, method='poisson', normalization='combinatorial', tau=0, X=None, alpha=2, zeta=1e7, r=0.1):
         """Reweight the graph more heavily near the labelled nodes `idx` (reference

@@ -466,12 +466,20 @@ def _poisson_source(n, train_ind, train_labels):
     return source, k
 
 
+class _NoOperator:
+    """Stands where a learner's cache keeps its device operator when the cached thing lives on the host."""
+
+    def close(self):
+        pass
+
+
 class poisson(ssl):
     def __init__(self, W=None, class_priors=None, solver='conjugate_gradient', p=1, use_cuda=False, min_iter=50,
                  max_iter=1000, tol=1e-3, spectral_cutoff=10):
-        """Poisson learning, reference ssl.py:513-693.  Solvers 'conjugate_gradient'
-        (default) and 'gradient_descent' run on the GPU; 'spectral' (an eigensolver) is out
-        of this package's scope."""
+        """Poisson learning, reference ssl.py:513-693.  Solvers 'conjugate_gradient' (default) and 'gradient_descent' run on the
+        GPU.  'spectral' (what p != 1 switches to, as in the reference) takes the spectral_cutoff + 1 lowest random-walk eigenpairs
+        of the graph without its diagonal from graph.eigen_decomp -- thick-restart Lanczos on the GPU, with that method's stated
+        deviations and run-time errors -- once per graph, and forms V (L (V^T source)) in host numpy (reference ssl.py:680-688)."""
         super().__init__(W, class_priors)
         if solver not in ['conjugate_gradient', 'spectral', 'gradient_descent']:
             sys.exit('Invalid Poisson solver')
@@ -504,11 +512,21 @@ class poisson(ssl):
         626-627, 634-635, 642-644): zero the diagonal, degrees, P = D^-1 W^T or the
         normalised Laplacian; uploaded once and kept on the device."""
         fp = self._graph_key()
-        key = (fp, self.solver, self._dtype())
+        key = (fp, self.solver, self._dtype()) + ((self.spectral_cutoff,) if self.solver == 'spectral' else ())
         if self._cache is not None and self._cache[0] == key:
             return self._cache[1], self._cache[2]
         n = self.graph.num_nodes
         W = self.graph.weight_matrix
+        if self.solver == 'spectral':        # reference ssl.py:615-617, 682: the decomposition depends on the graph only
+            G = graph_mod.graph(W - sparse.spdiags(W.diagonal(), 0, n, n))
+            vals, vecs = G.eigen_decomp(normalization='randomwalk', k=self.spectral_cutoff + 1, device=self.device)
+            if self._cache is not None:
+                for name in ('sweep', 'groups'):
+                    if self._cache[2].get(name) is not None:
+                        self._cache[2][name].close()
+                self._cache[1].close()
+            self._cache = (key, _NoOperator(), {'vals': vals, 'vecs': vecs, 'graph': G})
+            return self._cache[1], self._cache[2]
         # (a stamped matrix is weightmatrix.knn's output, unchanged: symmetric bit for bit, no diagonal, no stored zeros)
         fast = self.solver != 'conjugate_gradient' and utils.known_symmetric(W, fp)
         if not fast:
@@ -642,9 +660,15 @@ class poisson(ssl):
                     u = self.prob
                 elif isinstance(u, _DeviceState):      # no sweep ran: u = 0 (ssl.py:645), not whatever a previous fit left in `prob`
                     u = np.zeros((n, k), dtype=self._dtype())
-        elif self.solver == 'spectral':
-            raise NotImplementedError("poisson(solver='spectral') needs an eigensolver, which is outside the "
-                                      'GPU hot path this package covers (SURVEY.md section 8)')
+        elif self.solver == 'spectral':               # reference ssl.py:680-688
+            source, k = _poisson_source(n, train_ind, train_labels)
+            _, aux = self._operators()
+            V = aux['vecs'][:, 1:]
+            vals = aux['vals'][1:]
+            if self.p != 1:
+                vals = vals ** self.p
+            L = sparse.spdiags(1 / vals, 0, self.spectral_cutoff, self.spectral_cutoff)
+            u = V @ (L @ (V.T @ source))
         else:
             sys.exit('Invalid Poisson solver ' + self.solver)
         return u

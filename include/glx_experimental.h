@@ -269,6 +269,34 @@ int glx_ck_solve(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* co
                  double* l_out, int64_t* T_out, double* err_hist, int64_t err_cap, glx_ck_iterate_fn on_iterate, void* user,
                  int64_t* plan_out, int device);
 
+/* ---- thick-restart Lanczos eigensolver: graph.eigen_decomp, ssl.poisson(solver='spectral') (csrc/eig.hip, csrc/eig_plan.h) --------
+ * The device half of the solver for the k largest singular values of a symmetric matrix A (the method works on B = A A): a basis of
+ * m + 1 column-major Lanczos vectors that stays on the device, and the operations on it.  The host half -- the projected matrix, the
+ * stop, the restart, the probe for a missed multiple eigenvalue -- is graphlearning_amd/_eig.py.  Every operation is a pure function of
+ * its arguments in the order of DESIGN.md 4.12 (no fused multiply-add, no floating-point atomics) and equals EigHost of csrc/eig_plan.h
+ * bit for bit.  A arrives as canonical CSR: n rows, row_ptr (n + 1), col strictly ascending inside a row, val finite; a stored
+ * diagonal and empty rows are legal; symmetry is the caller's business.  1 <= m <= min(n, 513).  OWNERSHIP: the caller owns *out and
+ * releases it with glx_eig_destroy.  All pointers are host pointers; every call returns with its work complete.
+ * glx_eig_set_column: column j (0 .. m) <- host_vector (n).
+ * glx_eig_orthonormalize: column j (0 .. m) is made orthogonal to the columns before it (two passes of projection and update) and
+ *   scaled to length one; *norm_out = its length before the scaling.
+ * glx_eig_run: the Lanczos steps j0 <= j < j1 <= m, each reading the columns 0 .. j and writing column j + 1, enqueued without a
+ *   host wait in between; alpha_out, beta_out (j1 - j0): the coefficients of the steps.
+ * glx_eig_rotate: V[:, :keep] <- V[:, :rows] Y with Y (rows, keep) row-major, 1 <= keep <= rows <= m, every element summed in ascending
+ *   column order; then V[:, keep] <- V[:, rows].
+ * glx_eig_get_columns: out (j1 - j0, n) <- the columns j0 <= j < j1 <= m + 1, column j0 first.
+ * GLX_EINVAL: a null argument, rows that are not canonical, an index out of range, a value that is not finite, m or a column outside its
+ * range.  GLX_EUNSUPPORTED: more than 256 columns asked of glx_eig_get_columns.  GLX_ENOMEM: the (m + 3) n doubles of the basis and
+ * its two work vectors, the matrix and the partial sums exceed the device's memory. */
+typedef struct glx_eig glx_eig;
+int glx_eig_create(int64_t n, const int64_t* row_ptr, const int32_t* col, const double* val, int m, int device, glx_eig** out);
+int glx_eig_set_column(glx_eig* e, int j, const double* host_vector);
+int glx_eig_orthonormalize(glx_eig* e, int j, double* norm_out);
+int glx_eig_run(glx_eig* e, int j0, int j1, double* alpha_out, double* beta_out);
+int glx_eig_rotate(glx_eig* e, const double* Y, int rows, int keep);
+int glx_eig_get_columns(glx_eig* e, int j0, int j1, double* out);
+int glx_eig_destroy(glx_eig* e);
+
 #ifdef __cplusplus
 }
 #endif
