@@ -161,6 +161,8 @@ _SIGNATURES = {
                              C.c_int],
     'glx_ck_solve': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp,
                      _f64p, _i64p, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
+    'glx_mmbo_solve': [C.c_int64, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, _vp, _vp, _vp,
+                       C.c_int],
     'glx_eig_create': [C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
     'glx_eig_set_column': [_vp, C.c_int, _vp],
     'glx_eig_orthonormalize': [_vp, C.c_int, _f64p],
@@ -1232,6 +1234,30 @@ def ck_solve(row_ptr, col, W, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e
 
 
 _CK_ITERATE_FN = C.CFUNCTYPE(C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_double, _vp)
+
+
+def mmbo_solve(X, vals, lab0, ind, lab, k, Ns=6, T=10, dt=0.15, mu=50, device=None):
+    """The multiclass MBO learner's T * Ns diffusion steps and T projections in one device call (glx_mmbo_solve, csrc/mmbo.hip; the
+    contract is DESIGN.md 4.13): the basis X (n, m) with vals (m) -- any finite arrays, the learner hands in eigenpairs --, the start
+    labels lab0 (n) in [0, k), the training vertices `ind` with their labels `lab`.  Returns (labels (T, n) int32 after every outer
+    iteration, the last row being the result; the last Z (k, m) float64; plan = (launches per step, rows per partial sum, partial
+    sums, the caps on k * m, k and m, launches enqueued)).  GlxError (GLX_EUNSUPPORTED) above the caps, before anything is touched."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    vals = np.ascontiguousarray(vals, dtype=np.float64).ravel()
+    lab0 = np.ascontiguousarray(lab0, dtype=np.int32).ravel()
+    ind = np.ascontiguousarray(ind, dtype=np.int32).ravel()
+    lab = np.ascontiguousarray(lab, dtype=np.int32).ravel()
+    k, Ns, T = int(k), int(Ns), int(T)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or vals.shape != (X.shape[1],) or lab0.shape != (X.shape[0],) or ind.shape != lab.shape:
+        raise GlxError('mmbo_solve: inconsistent array shapes or sizes')
+    n, m = X.shape
+    ok = 1 <= k and 1 <= T and T * n <= 1 << 31 and k * m <= 1 << 16          # (the call refuses; only the result arrays depend on it)
+    hist = np.empty((T, n) if ok else (1, 1), dtype=np.int32)
+    Z = np.empty((k, m) if ok else (1, 1), dtype=np.float64)
+    plan = (C.c_int64 * 7)(0, 0, 0, 0, 0, 0, 0)
+    check(load().glx_mmbo_solve(n, m, _ptr(X), _ptr(vals), _ptr(lab0), len(ind), _ptr(ind), _ptr(lab), k, Ns, T, float(dt), float(mu), _ptr(hist),
+                                _ptr(Z), plan, _dev(device)), 'glx_mmbo_solve')
+    return hist, Z, tuple(int(v) for v in plan)
 
 
 class Eig:

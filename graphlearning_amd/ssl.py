@@ -1464,6 +1464,84 @@ class centered_kernel(ssl):
         return u
 
 
+MMBO_CAP = 4096          # classes times eigenvectors at most (csrc/mmbo_plan.h: Z is held in LDS)
+
+
+class multiclass_mbo(ssl):
+    def __init__(self, W=None, class_priors=None, Ns=6, T=10, dt=0.15, mu=50, num_eig=50):
+        """Multiclass MBO (reference ssl.py:912-1005; Garcia-Cardona, Merkurjev, Bertozzi, Flenner and Percus, IEEE PAMI 2014): T outer
+        iterations of Ns diffusion steps in the basis of the num_eig lowest eigenvectors of the normalised Laplacian, with a fidelity
+        term of weight mu on the training vertices, each followed by the projection of every vertex onto its largest class.  The
+        decomposition is graph.eigen_decomp('normalized', k=num_eig), cached in the graph; all T * Ns steps and T projections are one
+        device call (_hip.mmbo_solve; the contract is DESIGN.md 4.13).  `prob` is the one-hot matrix of the last projection, (n, k)
+        with entries exactly 0.0 and 1.0, as in the reference.  Not one-vs-rest.
+
+        The random start is ONE call np.random.rand(k, n) on numpy's global stream, then argmax over the classes.  Seeding caveat:
+        the reference draws after its eigen_decomp, whose ARPACK start vector comes from the same stream, and this package's
+        eigen_decomp does not touch the stream -- so the same np.random.seed gives another start here than in the reference.  A
+        caller who needs the reference's start restores the stream's state at that draw (np.random.set_state).  From the same start
+        the labels equal the reference's wherever no vertex's two largest entries come within rounding of each other.
+
+        After a fit: `num_iter` (T * Ns) and `mmbo_plan`.  With `all_labels` the reference's line `Accuracy = ..` per outer iteration
+        is printed after the solve, from the labels the call records.  Refused with ValueError before any device call: Ns < 1, T < 1
+        or T * Ns > 2^24, dt or mu not finite, a training index out of range, labels that are not exactly 0 .. k-1, index and label
+        arrays of different lengths, an empty training set, more than 256 classes, k * num_eig above 4096, eigenvalues or
+        eigenvectors that are not finite (only eigenpairs a caller put into graph.eigendata can be).  eigen_decomp's own refusals
+        and GlxErrors pass through."""
+        super().__init__(W, class_priors)
+        self.Ns = Ns
+        self.T = T
+        self.dt = dt
+        self.mu = mu
+        self.num_eig = num_eig
+        self.requires_eig = True
+        self.accuracy_filename = '_multiclass_mbo_Ns_%d_T_%d_dt_%.3f_mu_%.2f' % (Ns, T, dt, mu)
+        self.name = 'Multiclass MBO'
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        n = self.graph.num_nodes
+        train_ind = np.asarray(train_ind).ravel()
+        train_labels = np.asarray(train_labels).ravel()
+        Ns, T = self.Ns, self.T
+        if not (Ns == int(Ns) and T == int(T) and int(Ns) >= 1 and int(T) >= 1 and int(T) * int(Ns) <= 1 << 24):
+            raise ValueError('multiclass_mbo: Ns=%r and T=%r must be whole numbers, at least 1, with T * Ns at most 2^24' % (Ns, T))
+        Ns, T = int(Ns), int(T)
+        if not (np.isfinite(self.dt) and np.isfinite(self.mu)):
+            raise ValueError('multiclass_mbo: dt=%r or mu=%r is not finite' % (self.dt, self.mu))
+        if len(train_ind) != len(train_labels):
+            raise ValueError('multiclass_mbo: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
+        if len(train_ind) == 0:
+            raise ValueError('multiclass_mbo: no training vertex')
+        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
+            raise ValueError('multiclass_mbo: train_ind out of range (or not an integer array)')
+        classes = np.unique(train_labels)
+        k = len(classes)
+        if not np.array_equal(classes, np.arange(k)):
+            raise ValueError('multiclass_mbo: the labels are not exactly 0 .. %d' % (k - 1))
+        if k > 256:
+            raise ValueError('multiclass_mbo: %d classes, at most 256 per call' % k)
+        if k * int(self.num_eig) > MMBO_CAP:
+            raise ValueError('multiclass_mbo: %d classes times num_eig=%d is above the limit of %d' % (k, int(self.num_eig), MMBO_CAP))
+        vals, X = self.graph.eigen_decomp(normalization='normalized', k=self.num_eig)
+        if not (np.all(np.isfinite(vals)) and np.all(np.isfinite(X))):
+            raise ValueError('multiclass_mbo: an eigenvalue or eigenvector entry is NaN or infinite')
+        labels = train_labels.astype(np.int32)
+        lab0 = np.argmax(np.random.rand(k, n), axis=0).astype(np.int32)
+        lab0[train_ind] = labels
+        hist, _, plan = _hip.mmbo_solve(X, vals, lab0, train_ind.astype(np.int32), labels, k, Ns=Ns, T=T, dt=float(self.dt), mu=float(self.mu),
+                                        device=self.device)
+        self.num_iter = T * Ns
+        self.mmbo_plan = plan
+        cls = np.arange(k, dtype=np.int32)[None, :]
+        if all_labels is not None:        # the reference's lines (ssl.py:999-1003), one per outer iteration, on the labels of each
+            for i in range(T):
+                self.prob = (hist[i][:, None] == cls).astype(np.float64)
+                acc = ssl_accuracy(self.predict(), all_labels, train_ind)
+                sys.stdout.write('Accuracy = %.2f\n' % acc)
+            sys.stdout.flush()
+        return (hist[T - 1][:, None] == cls).astype(np.float64)
+
+
 def ssl_accuracy(pred_labels, true_labels, train_ind):
     """Accuracy in percent over nodes outside train_ind with a true label >= 0
     (reference ssl.py:1795-1834: `100*np.mean(pred[mask] == true[mask])` over the masked arrays).  The same number from

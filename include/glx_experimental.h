@@ -269,6 +269,24 @@ int glx_ck_solve(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* co
                  double* l_out, int64_t* T_out, double* err_hist, int64_t err_cap, glx_ck_iterate_fn on_iterate, void* user,
                  int64_t* plan_out, int device);
 
+/* ---- multiclass MBO learner: ssl.multiclass_mbo (csrc/mmbo.hip, csrc/mmbo_plan.h) ------------------------------------------------
+ * The loop of the reference's ssl.multiclass_mbo (ssl.py:989-996; Garcia-Cardona et al. 2014) in one blocking call: T outer
+ * iterations of Ns diffusion steps Z = (u - c0 J (u - K)) (X diag(d)), u = Z X^T with c0 = (dt / Ns) mu and d[j] = 1 / (1 + (dt / Ns)
+ * vals[j]), each followed by the projection of every vertex onto its first largest class.  X (n, m) row-major and vals (m) are any
+ * finite arrays (the learner hands in eigenpairs of the normalised Laplacian); lab0 (n) are the start labels in [0, k), used as they
+ * are; the ntrain training vertices ind carry the labels lab in [0, k) (a vertex listed twice takes its last label; ntrain = 0 is
+ * legal).  The order of operations and of every sum is that of DESIGN.md 4.13, so the result is a pure function of the arguments (no
+ * floating-point atomics, no fused multiply-add) and equals mmbo_host_reference (csrc/mmbo_plan.h) bit for bit.  Two launches per
+ * step and one last pass for the labels; u is never stored.  hist (T, n): the labels after every outer iteration, the last row is the
+ * result.  Zlast (k, m): the Z of the last step.  plan_out[7] (or NULL): launches per step, rows per partial sum, partial sums, the
+ * caps on k * m, k and m, launches enqueued.  All pointers are host pointers.
+ * GLX_EINVAL: a null argument, bad sizes, Ns or T below 1 or T * Ns above 2^24, dt or mu not finite, a training vertex or a label out
+ * of range, X, vals or a factor d[j] not finite.  GLX_EUNSUPPORTED, before anything is touched: k > 256, m > 256, k * m > 4096 (Z is
+ * held in LDS), n * m, T * n or partial sums * k * m above 2^31. */
+int glx_mmbo_solve(int64_t n, int m, const double* X, const double* vals, const int32_t* lab0, int64_t ntrain, const int32_t* ind,
+                   const int32_t* lab, int k, int64_t Ns, int64_t T, double dt, double mu, int32_t* hist, double* Zlast, int64_t* plan_out,
+                   int device);
+
 /* ---- thick-restart Lanczos eigensolver: graph.eigen_decomp, ssl.poisson(solver='spectral') (csrc/eig.hip, csrc/eig_plan.h) --------
  * The device half of the solver for the k largest singular values of a symmetric matrix A (the method works on B = A A): a basis of
  * m + 1 column-major Lanczos vectors that stays on the device, and the operations on it.  The host half -- the projected matrix, the
