@@ -1,37 +1,38 @@
 // The centered-kernel learner of Mai and Couillet (ICML 2018) in one device call: the power iteration for the largest eigenvalue of
 // C W C and the fixed-point iteration u <- u + ((1 / alpha) C W C u - u) off the training rows, the loop of the reference's
 // ssl.centered_kernel (ssl.py:1346-1426), reached through ssl.centered_kernel / _hip.ck_solve.  The contract -- the one-pass form
-// C W C u = W u - d (x) m - 1 (x) yb, every operation rounded on its own, the reduction order, the stop -- is written down in
-// ck_plan.h and DESIGN.md 4.11 and walked on the host by ck_host_reference; this file is that loop on the device, bit for bit.
+// C W C u = W u - d (x) m - 1 (x) yb, every operation rounded on its own, the stop -- is written down in ck_plan.h and DESIGN.md 4.11,
+// the reduction order in fixed_sum.h, and both are walked on the host by ck_host_reference; this file is that loop on the device,
+// bit for bit.
 //
 // Two kernels per iteration with an ordinary kernel boundary between them (1.5-1.9 us; a cooperative grid-wide wait costs 26 us or
-// more, so there is none).  The pass: one thread per (vertex, column), columns fastest, a workgroup = the CK_ROWS rows of one partial
+// more, so there is none).  The pass: one thread per (vertex, column), columns fastest, a workgroup = the FS_ROWS rows of one partial
 // times one tile of at most CK_TILE columns.  A thread walks its row's entries alone and in stored order, the lanes of a row read
 // consecutive doubles of each gathered record; the iterate goes into the other of two buffers because the gathers read other rows.
-// The workgroup adds its rows' u' and c u' by a fixed tree in LDS and leaves one partial per column, and the maximum of |w| as a bit
-// pattern.  The finishing kernel, ONE workgroup, adds the partials in a fixed order (64 chains, then the same tree) and leaves m, yb
-// and the iteration's err slot -- no workgroup of the pass reads all partials, no floating-point atomic anywhere, nothing depends on
-// which workgroup ends first.  The power iteration is the same pair of kernels with one column and five sums.
+// The workgroup adds its rows' u' and c u' by the tree of fs_tree64 in LDS (ck_tree) and leaves one partial per column, and the
+// maximum of |w| as a bit pattern.  The finishing kernel, ONE workgroup, adds the partials in the order of fs_finish (fs_finish_cols
+// of fixed_sum_device.h) and leaves m, yb and the iteration's err slot -- no workgroup of the pass reads all partials, no
+// floating-point atomic anywhere, nothing depends on which workgroup ends first.  The power iteration is the same pair of kernels
+// with one column and five sums.
 //
 // The host enqueues chunks of CK_CHUNK iterations, reads the chunk's err slots once and decides (CkStops).  Both kernels first look at
 // the slot of the iteration before theirs, so whatever was enqueued behind the stop changes nothing.  Buffers come from the pool and
 // are written before they are read; no launch sequence is captured.
 #include "glx_internal.h"
 #include "ck_plan.h"
+#include "fixed_sum_device.h"
 #include <algorithm>
 #include <vector>
 
-#define CK_FIN_THREADS (CK_CHAINS * CK_FIN_COLS)
-
-// the workgroup's NQ sums over its CK_ROWS rows, thread (r, c) of a tile `ct` columns wide holding v[]: the tree of ck_tree64.
-// s: NQ * CK_ROWS * ct doubles of LDS.  The result is valid in the threads of row 0.
+// the workgroup's NQ sums over its FS_ROWS rows, thread (r, c) of a tile `ct` columns wide holding v[]: the tree of fs_tree64
+// (fixed_sum.h) in this kernel's own LDS layout.  s: NQ * FS_ROWS * ct doubles of LDS.  The result is valid in the threads of row 0.
 template <int NQ>
 __device__ __forceinline__ void ck_tree(double* v, double* s, int r, int c, int ct) {
 #pragma clang fp contract(off)
-  const int at = r * ct + c, plane = CK_ROWS * ct;
+  const int at = r * ct + c, plane = FS_ROWS * ct;
 #pragma unroll
   for (int j = 0; j < NQ; ++j) s[j * plane + at] = v[j];
-  for (int h = CK_ROWS / 2; h >= 1; h >>= 1) {
+  for (int h = FS_ROWS / 2; h >= 1; h >>= 1) {
     __syncthreads();
     if (r < h) {
 #pragma unroll
@@ -45,15 +46,15 @@ __device__ __forceinline__ void ck_tree(double* v, double* s, int r, int c, int 
 }
 
 // pst: nrm, m, yb of the vector x (read), l and 1 / alpha (written by the finishing kernel); part (P, 5): e.w, e.e, w.w, 1.w, c.w
-__global__ __launch_bounds__(CK_ROWS) void ck_power_pass_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+__global__ __launch_bounds__(FS_ROWS) void ck_power_pass_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                                  const double* __restrict__ W, const double* __restrict__ d,
                                                                  const double* __restrict__ cs, const double* __restrict__ x,
                                                                  double* __restrict__ xout, const double* __restrict__ pst,
                                                                  double* __restrict__ part, int64_t n) {
 #pragma clang fp contract(off)
-  __shared__ double s_t[5 * CK_ROWS];
+  __shared__ double s_t[5 * FS_ROWS];
   const int r = threadIdx.x;
-  const int64_t i = (int64_t)blockIdx.x * CK_ROWS + r;
+  const int64_t i = (int64_t)blockIdx.x * FS_ROWS + r;
   double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   if (i < n) {
     const double nrm = pst[0], mean = pst[1], yb = pst[2];
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(CK_ROWS) void ck_power_pass_kernel(const int64_t* _
 }
 
 // iteration of slot r: reads uin, mst = m[k], yb[k]; writes uout, part (P, 2 k) and perr (P, ntiles)
-__global__ __launch_bounds__(CK_ROWS * CK_TILE) void ck_pass_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+__global__ __launch_bounds__(FS_ROWS * CK_TILE) void ck_pass_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                                      const double* __restrict__ W, const double* __restrict__ d,
                                                                      const double* __restrict__ cs, const int32_t* __restrict__ lab,
                                                                      const double* __restrict__ uin, double* __restrict__ uout,
@@ -92,13 +93,13 @@ __global__ __launch_bounds__(CK_ROWS * CK_TILE) void ck_pass_kernel(const int64_
                                                                      int64_t n, int k, int ct, int tbase, int textra,
                                                                      const double* __restrict__ slots, int r_slot, double tol) {
 #pragma clang fp contract(off)
-  extern __shared__ double s_dyn[];          // 2 * CK_ROWS * ct doubles
+  extern __shared__ double s_dyn[];          // 2 * FS_ROWS * ct doubles
   __shared__ unsigned long long s_e;
   if (ck_stopped(slots[r_slot - 1], tol)) return;          // the iteration before was the last one
   const int r = (int)threadIdx.x / ct, c = (int)threadIdx.x - r * ct;
   const int tile = blockIdx.y;
   const int c0 = tile * tbase + (tile < textra ? tile : textra), cols = tbase + (tile < textra ? 1 : 0);
-  const int64_t i = (int64_t)blockIdx.x * CK_ROWS + r;
+  const int64_t i = (int64_t)blockIdx.x * FS_ROWS + r;
   if (threadIdx.x == 0) s_e = 0ull;
   double v[2] = {0.0, 0.0};
   unsigned long long eb = 0ull;
@@ -134,30 +135,21 @@ __global__ __launch_bounds__(CK_ROWS * CK_TILE) void ck_pass_kernel(const int64_
   if (threadIdx.x == 0) perr[(int64_t)blockIdx.x * gridDim.y + tile] = s_e;
 }
 
-// the sums of the nq columns of part (P, nq) into s_sum: chain q adds the partials q, q + 64, .. in order, then the tree over the chains
+// the sums of the nq columns of part (P, nq) into s_sum, FS_FIN_COLS of them per round; s_sum may be read when it returns
 __device__ __forceinline__ void ck_finish_sums(const double* __restrict__ part, int64_t P, int nq, double* s_a, double* s_sum) {
 #pragma clang fp contract(off)
-  const int q = (int)threadIdx.x / CK_FIN_COLS, cc = (int)threadIdx.x % CK_FIN_COLS;
-  for (int j0 = 0; j0 < nq; j0 += CK_FIN_COLS) {
-    const int j = j0 + cc;
-    double a = 0.0;
-    if (j < nq)
-      for (int64_t p = q; p < P; p += CK_CHAINS) a = a + part[p * nq + j];
-    s_a[q * CK_FIN_COLS + cc] = a;
-    for (int h = CK_CHAINS / 2; h >= 1; h >>= 1) {
-      __syncthreads();
-      if (q < h) s_a[q * CK_FIN_COLS + cc] = s_a[q * CK_FIN_COLS + cc] + s_a[(q + h) * CK_FIN_COLS + cc];
-    }
-    __syncthreads();
-    if (q == 0 && j < nq) s_sum[j] = s_a[cc];
-    __syncthreads();
+  for (int j0 = 0; j0 < nq; j0 += FS_FIN_COLS) {
+    const int j = j0 + (int)threadIdx.x % FS_FIN_COLS;
+    const double s = fs_finish_cols(part, P, nq, j0, s_a);
+    if ((int)threadIdx.x < FS_FIN_COLS && j < nq) s_sum[j] = s;
+    __syncthreads();          // s_a may be written again and s_sum read
   }
 }
 
-__global__ __launch_bounds__(CK_FIN_THREADS) void ck_power_finish_kernel(const double* __restrict__ part, int64_t P, double* pst, double sc,
+__global__ __launch_bounds__(FS_FIN_THREADS) void ck_power_finish_kernel(const double* __restrict__ part, int64_t P, double* pst, double sc,
                                                                           double invn, int last, double alpha_frac) {
 #pragma clang fp contract(off)
-  __shared__ double s_a[CK_FIN_THREADS];
+  __shared__ double s_a[FS_FIN_THREADS];
   __shared__ double s_sum[8];
   ck_finish_sums(part, P, 5, s_a, s_sum);
   if (threadIdx.x == 0) {
@@ -179,11 +171,11 @@ __global__ __launch_bounds__(CK_FIN_THREADS) void ck_power_finish_kernel(const d
 }
 
 // closes the iteration of slot r: m, yb of the new iterate and err; r_slot = 0: the start (the partials of u0, no err)
-__global__ __launch_bounds__(CK_FIN_THREADS) void ck_finish_kernel(const double* __restrict__ part, int64_t P, int k,
+__global__ __launch_bounds__(FS_FIN_THREADS) void ck_finish_kernel(const double* __restrict__ part, int64_t P, int k,
                                                                     const unsigned long long* __restrict__ perr, int64_t nerr, double* mst,
                                                                     double sc, double invn, double* slots, int r_slot, double tol) {
 #pragma clang fp contract(off)
-  __shared__ double s_a[CK_FIN_THREADS];
+  __shared__ double s_a[FS_FIN_THREADS];
   __shared__ double s_sum[2 * CK_MAX_COLS];
   __shared__ unsigned long long s_e;
   if (r_slot > 0 && ck_stopped(slots[r_slot - 1], tol)) return;
@@ -199,7 +191,7 @@ __global__ __launch_bounds__(CK_FIN_THREADS) void ck_finish_kernel(const double*
   }
   if (r_slot > 0) {
     unsigned long long e = 0ull;
-    for (int64_t q = threadIdx.x; q < nerr; q += CK_FIN_THREADS) e = perr[q] > e ? perr[q] : e;
+    for (int64_t q = threadIdx.x; q < nerr; q += FS_FIN_THREADS) e = perr[q] > e ? perr[q] : e;
     if (e) atomicMax(&s_e, e);
     __syncthreads();
     if (threadIdx.x == 0) slots[r_slot] = __longlong_as_double((long long)s_e);
@@ -278,10 +270,10 @@ extern "C" int glx_ck_solve(int64_t n, int64_t M, const int64_t* row_ptr, const 
   for (int64_t p = 0; p < power_it; ++p) {
     const double* x = (p & 1) ? d_xb : d_xa;
     double* xout = (p & 1) ? d_xa : d_xb;
-    hipLaunchKernelGGL(ck_power_pass_kernel, dim3((unsigned)P), dim3(CK_ROWS), 0, st, (const int64_t*)d_ptr, (const int32_t*)d_col,
+    hipLaunchKernelGGL(ck_power_pass_kernel, dim3((unsigned)P), dim3(FS_ROWS), 0, st, (const int64_t*)d_ptr, (const int32_t*)d_col,
                        (const double*)d_w, (const double*)d_d, (const double*)d_c, x, xout, (const double*)d_pst, d_part, n);
     GLX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ck_power_finish_kernel, dim3(1), dim3(CK_FIN_THREADS), 0, st, (const double*)d_part, P, d_pst, plan.sc, plan.invn,
+    hipLaunchKernelGGL(ck_power_finish_kernel, dim3(1), dim3(FS_FIN_THREADS), 0, st, (const double*)d_part, P, d_pst, plan.sc, plan.invn,
                        p + 1 == power_it ? 1 : 0, alpha_frac);
     GLX_HIP(hipGetLastError());
     launches += 2;
@@ -291,14 +283,14 @@ extern "C" int glx_ck_solve(int64_t n, int64_t M, const int64_t* row_ptr, const 
                      (const double*)d_val, n, k);
   GLX_HIP(hipGetLastError());
   GLX_UP(glx_upload(d_part, part0.data(), (size_t)P * 2 * k * 8, st, __func__));
-  hipLaunchKernelGGL(ck_finish_kernel, dim3(1), dim3(CK_FIN_THREADS), 0, st, (const double*)d_part, P, k, (const unsigned long long*)d_perr,
+  hipLaunchKernelGGL(ck_finish_kernel, dim3(1), dim3(FS_FIN_THREADS), 0, st, (const double*)d_part, P, k, (const unsigned long long*)d_perr,
                      nerr, d_mst, plan.sc, plan.invn, d_slots, 0, tol);
   GLX_HIP(hipGetLastError());
   launches += 2;
 
   const int tbase = k / plan.ntiles, textra = k % plan.ntiles;          // ck_tile: tile t starts at t * tbase + min(t, textra)
-  const dim3 grid((unsigned)P, (unsigned)plan.ntiles), blk((unsigned)(CK_ROWS * plan.ct));
-  const size_t lds = (size_t)2 * CK_ROWS * plan.ct * 8;
+  const dim3 grid((unsigned)P, (unsigned)plan.ntiles), blk((unsigned)(FS_ROWS * plan.ct));
+  const size_t lds = (size_t)2 * FS_ROWS * plan.ct * 8;
   std::vector<double> iterate;
   if (on_iterate) iterate.resize((size_t)n * k);
   CkStops stops(tol, max_it);
@@ -315,7 +307,7 @@ extern "C" int glx_ck_solve(int64_t n, int64_t M, const int64_t* row_ptr, const 
                          (const double*)d_d, (const double*)d_c, (const int32_t*)d_lab, uin, uout, (const double*)d_mst, (const double*)d_pst,
                          d_part, d_perr, n, k, plan.ct, tbase, textra, (const double*)d_slots, r, tol);
       GLX_HIP(hipGetLastError());
-      hipLaunchKernelGGL(ck_finish_kernel, dim3(1), dim3(CK_FIN_THREADS), 0, st, (const double*)d_part, P, k,
+      hipLaunchKernelGGL(ck_finish_kernel, dim3(1), dim3(FS_FIN_THREADS), 0, st, (const double*)d_part, P, k,
                          (const unsigned long long*)d_perr, nerr, d_mst, plan.sc, plan.invn, d_slots, r, tol);
       GLX_HIP(hipGetLastError());
       launches += 2;

@@ -9,13 +9,10 @@
 //     s  = sum over the row's stored entries in order, from +0.0, of W[e] * u[col[e], b]
 //     w  = inva * ((s - d[i] * m[b]) - yb[b]) - u[i, b];      w = 0 on a training row
 //     u' = u[i, b] + w
-// and leaves, per partial of CK_ROWS consecutive rows, the sums of u' and of c[i] * u' and the integer maximum of the bit patterns of
+// and leaves, per partial of FS_ROWS consecutive rows, the sums of u' and of c[i] * u' and the integer maximum of the bit patterns of
 // |w| (non-negative doubles order like their bit patterns, and a NaN's pattern lies above every number's: a NaN reaches the slot).
 //
-// The reduction order.  Rows [64 p, 64 p + 64) form partial p whatever k is; rows past n count as +0.0.  Inside a partial the 64
-// values are added by a halving tree: a[r] += a[r + h] for r < h, h = 32, 16, .. 1 (ck_tree64).  The partials of a column are
-// finished by 64 chains -- chain q adds the partials p = q, q + 64, .. in ascending order from +0.0 -- and the same tree over the
-// chains (ck_finish).  Nothing depends on which workgroup ends first.
+// The reduction order is the one of fixed_sum.h: the 64 rows of a partial by fs_tree64, the partials of a column by fs_finish.
 //
 // The power iteration is the same pass with one column: x is e at first and the unnormalised product afterwards, e_i = x_i / nrm
 // formed where it is read, w = (W e - d * m) - yb, and the partials of e.w, e.e, w.w, 1.w and c.w give l = |e.w / e.e|,
@@ -26,6 +23,7 @@
 // the very start).  A pass and its finishing kernel first look at the slot before theirs and do nothing when !(slot > tol): after the
 // stop every later slot stays NaN, which stops as well, whatever tol is.
 #pragma once
+#include "fixed_sum.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -33,10 +31,7 @@
 #include <limits>
 #include <vector>
 
-static const int CK_ROWS = 64;             // rows per partial sum
-static const int CK_TILE = 16;             // columns per workgroup of the pass at most (CK_ROWS * CK_TILE threads)
-static const int CK_CHAINS = 64;           // chains of the finishing kernel
-static const int CK_FIN_COLS = 16;         // columns the finishing kernel reduces per round (CK_CHAINS * CK_FIN_COLS threads)
+static const int CK_TILE = 16;             // columns per workgroup of the pass at most (FS_ROWS * CK_TILE threads)
 static const int CK_CHUNK = 64;            // iterations enqueued between two reads of the error slots
 static const int CK_MAX_COLS = 256;
 static const int64_t CK_MAX_IT = 1ll << 24;
@@ -45,7 +40,7 @@ struct CkPlan {
   std::vector<double> c, d;                // (n) column and row sums of W
   std::vector<int32_t> lab;                // (n) the row of `val` a training vertex starts from (the last one that lists it), -1 elsewhere
   double sc = 0, invn = 0;
-  int64_t P = 0;                           // partials: ceil(n / CK_ROWS)
+  int64_t P = 0;                           // partials: fs_partials(n)
   int ntiles = 0, ct = 0;                  // column tiles of the pass and the widest tile's columns
 };
 
@@ -137,28 +132,8 @@ inline void ck_make_plan(int64_t n, const int64_t* row_ptr, const int32_t* col, 
   P.invn = 1.0 / (double)n;
   P.lab.assign((size_t)n, -1);
   for (int64_t q = 0; q < m; ++q) P.lab[ind[q]] = (int32_t)q;
-  P.P = (n + CK_ROWS - 1) / CK_ROWS;
+  P.P = fs_partials(n);
   ck_tiles(k, &P.ntiles, &P.ct);
-}
-
-// a[0] <- the halving tree over a[0 .. 64)
-inline double ck_tree64(double* a) {
-  for (int h = 32; h >= 1; h >>= 1)
-    for (int r = 0; r < h; ++r) a[r] = a[r] + a[r + h];
-  return a[0];
-}
-
-// S[j] for the nq columns of part (P, nq): 64 chains in ascending order, then the tree
-inline void ck_finish(const double* part, int64_t P, int nq, double* S) {
-  double a[CK_CHAINS];
-  for (int j = 0; j < nq; ++j) {
-    for (int q = 0; q < CK_CHAINS; ++q) {
-      double s = 0.0;
-      for (int64_t p = q; p < P; p += CK_CHAINS) s = s + part[p * nq + j];
-      a[q] = s;
-    }
-    S[j] = ck_tree64(a);
-  }
 }
 
 // the start of the fixed-point iteration: u0 = val on the training rows, zero elsewhere, and its (P, 2 k) partials (sums of u0, then
@@ -167,22 +142,22 @@ inline void ck_start_partials(const CkPlan& plan, int64_t n, int k, const double
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  double a[CK_ROWS], b[CK_ROWS];
+  double a[FS_ROWS], b[FS_ROWS];
   for (int64_t p = 0; p < plan.P; ++p) {
-    const int64_t i0 = p * CK_ROWS;
+    const int64_t i0 = p * FS_ROWS;
     bool any = false;
-    for (int r = 0; r < CK_ROWS && i0 + r < n; ++r) any = any || plan.lab[i0 + r] >= 0;
+    for (int r = 0; r < FS_ROWS && i0 + r < n; ++r) any = any || plan.lab[i0 + r] >= 0;
     for (int c = 0; c < k; ++c) {
       double s1 = 0.0, s2 = 0.0;
       if (any) {
-        for (int r = 0; r < CK_ROWS; ++r) {
+        for (int r = 0; r < FS_ROWS; ++r) {
           const int64_t i = i0 + r;
           const double v = (i < n && plan.lab[i] >= 0) ? val[(int64_t)plan.lab[i] * k + c] : 0.0;
           a[r] = v;
           b[r] = i < n ? plan.c[i] * v : 0.0;
         }
-        s1 = ck_tree64(a);
-        s2 = ck_tree64(b);
+        s1 = fs_tree64(a);
+        s2 = fs_tree64(b);
       }
       part[p * 2 * k + c] = s1;
       part[p * 2 * k + k + c] = s2;
@@ -208,18 +183,18 @@ inline void ck_power_start(const CkPlan& plan, int64_t n, const double* e, doubl
 #pragma clang fp contract(off)
 #endif
   std::vector<double> part((size_t)plan.P * 2);
-  double a[CK_ROWS], b[CK_ROWS];
+  double a[FS_ROWS], b[FS_ROWS];
   for (int64_t p = 0; p < plan.P; ++p) {
-    for (int r = 0; r < CK_ROWS; ++r) {
-      const int64_t i = p * CK_ROWS + r;
+    for (int r = 0; r < FS_ROWS; ++r) {
+      const int64_t i = p * FS_ROWS + r;
       a[r] = i < n ? e[i] : 0.0;
       b[r] = i < n ? plan.c[i] * e[i] : 0.0;
     }
-    part[p * 2] = ck_tree64(a);
-    part[p * 2 + 1] = ck_tree64(b);
+    part[p * 2] = fs_tree64(a);
+    part[p * 2 + 1] = fs_tree64(b);
   }
   double S[2];
-  ck_finish(part.data(), plan.P, 2, S);
+  fs_finish(part.data(), plan.P, 2, S);
   ck_means(S[0], S[1], plan.sc, plan.invn, mean, yb);
 }
 
@@ -272,10 +247,10 @@ inline void ck_host_power_pass(const CkPlan& plan, int64_t n, const int64_t* row
 #pragma clang fp contract(off)
 #endif
   std::vector<double> part((size_t)plan.P * 5);
-  double a[5][CK_ROWS];
+  double a[5][FS_ROWS];
   for (int64_t p = 0; p < plan.P; ++p) {
-    for (int r = 0; r < CK_ROWS; ++r) {
-      const int64_t i = p * CK_ROWS + r;
+    for (int r = 0; r < FS_ROWS; ++r) {
+      const int64_t i = p * FS_ROWS + r;
       for (int j = 0; j < 5; ++j) a[j][r] = 0.0;
       if (i >= n) continue;
       double s = 0.0;
@@ -295,9 +270,9 @@ inline void ck_host_power_pass(const CkPlan& plan, int64_t n, const int64_t* row
       a[3][r] = w;
       a[4][r] = plan.c[i] * w;
     }
-    for (int j = 0; j < 5; ++j) part[p * 5 + j] = ck_tree64(a[j]);
+    for (int j = 0; j < 5; ++j) part[p * 5 + j] = fs_tree64(a[j]);
   }
-  ck_finish(part.data(), plan.P, 5, S);
+  fs_finish(part.data(), plan.P, 5, S);
 }
 
 // what the finishing kernel of a power pass leaves
@@ -318,10 +293,10 @@ inline double ck_host_pass(const CkPlan& plan, int64_t n, const int64_t* row_ptr
 #pragma clang fp contract(off)
 #endif
   uint64_t emax = 0;
-  std::vector<double> a((size_t)2 * k * CK_ROWS);
+  std::vector<double> a((size_t)2 * k * FS_ROWS);
   for (int64_t p = 0; p < plan.P; ++p) {
-    for (int r = 0; r < CK_ROWS; ++r) {
-      const int64_t i = p * CK_ROWS + r;
+    for (int r = 0; r < FS_ROWS; ++r) {
+      const int64_t i = p * FS_ROWS + r;
       for (int c = 0; c < k; ++c) {
         double v1 = 0.0, v2 = 0.0;
         if (i < n) {
@@ -344,11 +319,11 @@ inline double ck_host_pass(const CkPlan& plan, int64_t n, const int64_t* row_ptr
           const uint64_t bits = __builtin_bit_cast(uint64_t, std::fabs(w));
           emax = bits > emax ? bits : emax;
         }
-        a[(size_t)c * CK_ROWS + r] = v1;
-        a[(size_t)(k + c) * CK_ROWS + r] = v2;
+        a[(size_t)c * FS_ROWS + r] = v1;
+        a[(size_t)(k + c) * FS_ROWS + r] = v2;
       }
     }
-    for (int j = 0; j < 2 * k; ++j) part[p * 2 * k + j] = ck_tree64(&a[(size_t)j * CK_ROWS]);
+    for (int j = 0; j < 2 * k; ++j) part[p * 2 * k + j] = fs_tree64(&a[(size_t)j * FS_ROWS]);
   }
   return __builtin_bit_cast(double, emax);
 }
@@ -382,7 +357,7 @@ inline int ck_host_reference(int64_t n, const int64_t* row_ptr, const int32_t* c
     if (plan.lab[i] >= 0)
       for (int c = 0; c < k; ++c) buf[0][i * k + c] = val[(int64_t)plan.lab[i] * k + c];
   ck_start_partials(plan, n, k, val, part.data());
-  ck_finish(part.data(), plan.P, 2 * k, S.data());
+  fs_finish(part.data(), plan.P, 2 * k, S.data());
   for (int c = 0; c < k; ++c) ck_means(S[c], S[k + c], plan.sc, plan.invn, &mk[c], &yk[c]);
   std::vector<double> slots((size_t)chunk + 1);
   CkStops stops(tol, max_it);
@@ -394,7 +369,7 @@ inline int ck_host_reference(int64_t n, const int64_t* row_ptr, const int32_t* c
       if (ck_stopped(slots[r - 1], tol)) continue;           // launches after the stop change nothing
       const int64_t q = stops.it + r;
       slots[r] = ck_host_pass(plan, n, row_ptr, col, W, k, inva, buf[(q - 1) & 1].data(), mk.data(), yk.data(), buf[q & 1].data(), part.data());
-      ck_finish(part.data(), plan.P, 2 * k, S.data());
+      fs_finish(part.data(), plan.P, 2 * k, S.data());
       for (int c = 0; c < k; ++c) ck_means(S[c], S[k + c], plan.sc, plan.invn, &mk[c], &yk[c]);
     }
     stops.decide(slots.data() + 1, len, err_hist, cap);

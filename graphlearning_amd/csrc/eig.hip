@@ -1,25 +1,24 @@
 // Thick-restart Lanczos with full reorthogonalisation on B = A A, the device half: graph.eigen_decomp and ssl.poisson(solver=
 // 'spectral') reach it through _hip.Eig and the driver of graphlearning_amd/_eig.py.  The contract -- the order of every sum, every
-// operation rounded on its own -- is written down in eig_plan.h and DESIGN.md 4.12 and walked on the host by EigHost; this file is
-// those operations on the device, bit for bit.  The host owns every decision (the projected matrix, the stop, the restart, the probe);
-// the device owns the basis, which never leaves it before the end.
+// operation rounded on its own -- is written down in eig_plan.h, fixed_sum.h and DESIGN.md 4.12 and walked on the host by EigHost;
+// this file is those operations on the device, bit for bit.  The host owns every decision (the projected matrix, the stop, the
+// restart, the probe); the device owns the basis, which never leaves it before the end.
 //
 // The basis is column-major, so projection and update stream (j + 1) n doubles with consecutive lanes on consecutive rows.  A
-// wavefront owns the 64 rows of one partial: the halving tree of ck_tree64 runs across its lanes (lane r takes lane r + h for
-// h = 32 .. 1; only the lanes below h hold meaningful sums, and those are the ones read); a workgroup holds EIG_WG_PARTIALS
-// wavefronts -- one, which spreads the 1 094 partials of 70 000 rows most evenly over the SIMDs (EXPERIMENTS.md "Eigensolver").  The partials of a column are finished by one workgroup per 16 columns in the order of ck_finish (64 chains, then the
-// tree): no floating-point atomic anywhere, nothing depends on which workgroup ends first.  The SpMV is a CSR row pass, one thread per row.
-// One step is eleven launches with ordinary kernel boundaries between them; all steps of a run are enqueued without a host wait and
-// alpha, beta come back once per run.  The rotation of a restart reads EIG_ROT_ROWS rows of the basis into LDS and writes them back
-// in place, each element summed in ascending column order -- which is why it is no MFMA product.
+// wavefront owns the 64 rows of one partial: the halving tree of fs_tree64 runs across its lanes (fs_wave_tree64 of
+// fixed_sum_device.h); a workgroup holds EIG_WG_PARTIALS wavefronts -- one, which spreads the 1 094 partials of 70 000 rows most
+// evenly over the SIMDs (EXPERIMENTS.md "Eigensolver").  The partials of a column are finished by one workgroup per 16 columns in the
+// order of fs_finish (fs_finish_cols): no floating-point atomic anywhere, nothing depends on which workgroup ends first.  The SpMV is
+// a CSR row pass, one thread per row.  One step is eleven launches with ordinary kernel boundaries between them; all steps of a run
+// are enqueued without a host wait and alpha, beta come back once per run.  The rotation of a restart reads EIG_ROT_ROWS rows of the
+// basis into LDS and writes them back in place, each element summed in ascending column order -- which is why it is no MFMA product.
 #include "glx_internal.h"
 #include "eig_plan.h"
+#include "fixed_sum_device.h"
 #include <mutex>
 #include <vector>
 
-#define EIG_WG (CK_ROWS * EIG_WG_PARTIALS)
-#define EIG_FIN_COLS 16
-#define EIG_FIN_THREADS (CK_CHAINS * EIG_FIN_COLS)
+#define EIG_WG (FS_ROWS * EIG_WG_PARTIALS)
 
 struct glx_eig {
   int64_t n = 0, nnz = 0, P = 0;
@@ -29,14 +28,6 @@ struct glx_eig {
   double *d_val = nullptr, *d_V = nullptr, *d_w = nullptr, *d_t = nullptr, *d_part = nullptr, *d_h = nullptr, *d_ab = nullptr, *d_Y = nullptr;
   std::mutex mu;          // one call at a time per object (ctypes releases the GIL)
 };
-
-// the tree of ck_tree64 over the 64 lanes of a wavefront; the sum is valid in lane 0
-__device__ __forceinline__ double eig_tree64(double a) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int h = CK_ROWS / 2; h >= 1; h >>= 1) a = a + __shfl_down(a, h, CK_ROWS);
-  return a;
-}
 
 __global__ __launch_bounds__(256) void eig_spmv_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                         const double* __restrict__ val, const double* __restrict__ x,
@@ -53,15 +44,16 @@ __global__ __launch_bounds__(256) void eig_spmv_kernel(const int64_t* __restrict
   y[i] = s;
 }
 
-// part[p][c] = the tree over the rows of partial p of v_c[i] * w[i], c < count.  Four columns at a time: their trees are independent,
-// and with one wavefront per SIMD at 70 000 rows it is the latency of the six dependent cross-lane steps that has to be hidden.
+// part[p][c] = the tree over the rows of partial p of v_c[i] * w[i], c < count.  Four columns at a time (fs_wave_tree64 of four): their
+// trees are independent, and with one wavefront per SIMD at 70 000 rows it is the latency of the six dependent cross-lane steps that
+// has to be hidden.
 __global__ __launch_bounds__(EIG_WG) void eig_dots_kernel(const double* __restrict__ V, int count, const double* __restrict__ w,
                                                            double* __restrict__ part, int64_t n, int64_t P) {
 #pragma clang fp contract(off)
-  const int64_t p = (int64_t)blockIdx.x * ((int)blockDim.x / CK_ROWS) + (int)threadIdx.x / CK_ROWS;
+  const int64_t p = (int64_t)blockIdx.x * ((int)blockDim.x / FS_ROWS) + (int)threadIdx.x / FS_ROWS;
   if (p >= P) return;                                   // (the same for every lane of the wavefront)
-  const int r = (int)threadIdx.x % CK_ROWS;
-  const int64_t i = p * CK_ROWS + r;
+  const int r = (int)threadIdx.x % FS_ROWS;
+  const int64_t i = p * FS_ROWS + r;
   const bool live = i < n;
   const double wi = live ? w[i] : 0.0;
   const double* v = V + (live ? i : 0);
@@ -73,11 +65,7 @@ __global__ __launch_bounds__(EIG_WG) void eig_dots_kernel(const double* __restri
       const double pr = v[(int64_t)(c + u) * n] * wi;
       a[u] = live ? pr : 0.0;
     }
-#pragma unroll
-    for (int h = CK_ROWS / 2; h >= 1; h >>= 1) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] = a[u] + __shfl_down(a[u], h, CK_ROWS);
-    }
+    fs_wave_tree64(a);
     if (r == 0) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) part[p * count + c + u] = a[u];
@@ -85,7 +73,7 @@ __global__ __launch_bounds__(EIG_WG) void eig_dots_kernel(const double* __restri
   }
   for (; c < count; ++c) {
     const double pr = v[(int64_t)c * n] * wi;
-    const double s = eig_tree64(live ? pr : 0.0);
+    const double s = fs_wave_tree64(live ? pr : 0.0);
     if (r == 0) part[p * count + c] = s;
   }
 }
@@ -94,10 +82,10 @@ __global__ __launch_bounds__(EIG_WG) void eig_dots_kernel(const double* __restri
 __global__ __launch_bounds__(EIG_WG) void eig_update_kernel(const double* __restrict__ V, int count, const double* __restrict__ h,
                                                              double* __restrict__ w, double* __restrict__ part_ww, int64_t n, int64_t P) {
 #pragma clang fp contract(off)
-  const int64_t p = (int64_t)blockIdx.x * ((int)blockDim.x / CK_ROWS) + (int)threadIdx.x / CK_ROWS;
+  const int64_t p = (int64_t)blockIdx.x * ((int)blockDim.x / FS_ROWS) + (int)threadIdx.x / FS_ROWS;
   if (p >= P) return;
-  const int r = (int)threadIdx.x % CK_ROWS;
-  const int64_t i = p * CK_ROWS + r;
+  const int r = (int)threadIdx.x % FS_ROWS;
+  const int64_t i = p * FS_ROWS + r;
   const bool live = i < n;
   double wi = live ? w[i] : 0.0;
   const double* v = V + (live ? i : 0);
@@ -109,31 +97,21 @@ __global__ __launch_bounds__(EIG_WG) void eig_update_kernel(const double* __rest
   if (live) w[i] = wi;
   if (part_ww) {
     const double sq = wi * wi;
-    const double s = eig_tree64(live ? sq : 0.0);
+    const double s = fs_wave_tree64(live ? sq : 0.0);
     if (r == 0) part_ww[p] = s;
   }
 }
 
-// ck_finish on the device: workgroup b owns the columns [16 b, 16 b + 16) of part (P, nq) and leaves out[j] = the sum of column j --
-// 64 chains in ascending order, then the tree over the chains; no workgroup depends on another.  mode 1: also *slot = prev[nq - 1] +
-// out[nq - 1] (alpha); mode 2 (nq = 1): out[0] = *slot = sqrt(sum) (beta)
-__global__ __launch_bounds__(EIG_FIN_THREADS) void eig_finish_kernel(const double* __restrict__ part, int64_t P, int nq, double* __restrict__ out,
+// fs_finish on the device: workgroup b owns the columns [16 b, 16 b + 16) of part (P, nq) and leaves out[j] = the sum of column j;
+// no workgroup depends on another.  mode 1: also *slot = prev[nq - 1] + out[nq - 1] (alpha); mode 2 (nq = 1): out[0] = *slot =
+// sqrt(sum) (beta)
+__global__ __launch_bounds__(FS_FIN_THREADS) void eig_finish_kernel(const double* __restrict__ part, int64_t P, int nq, double* __restrict__ out,
                                                                       int mode, const double* __restrict__ prev, double* __restrict__ slot) {
 #pragma clang fp contract(off)
-  __shared__ double s_a[EIG_FIN_THREADS];
-  const int q = (int)threadIdx.x / EIG_FIN_COLS, cc = (int)threadIdx.x % EIG_FIN_COLS;
-  const int j = (int)blockIdx.x * EIG_FIN_COLS + cc;
-  double a = 0.0;
-  if (j < nq)
-    for (int64_t p = q; p < P; p += CK_CHAINS) a = a + part[p * nq + j];
-  s_a[q * EIG_FIN_COLS + cc] = a;
-  for (int h = CK_CHAINS / 2; h >= 1; h >>= 1) {
-    __syncthreads();
-    if (q < h) s_a[q * EIG_FIN_COLS + cc] = s_a[q * EIG_FIN_COLS + cc] + s_a[(q + h) * EIG_FIN_COLS + cc];
-  }
-  __syncthreads();
-  if (q == 0 && j < nq) {
-    const double s = s_a[cc];
+  __shared__ double s_a[FS_FIN_THREADS];
+  const int j = (int)blockIdx.x * FS_FIN_COLS + (int)threadIdx.x;          // (of the threads of chain 0)
+  const double s = fs_finish_cols(part, P, nq, (int)blockIdx.x * FS_FIN_COLS, s_a);
+  if ((int)threadIdx.x < FS_FIN_COLS && j < nq) {
     if (mode == 2) {
       const double b = sqrt(s);
       out[j] = b;
@@ -210,7 +188,7 @@ static int eig_orthogonalise(glx_eig* e, int count, int dst, double* alpha_slot,
     if (count > 0) {
       hipLaunchKernelGGL(eig_dots_kernel, dim3(gw), dim3(wg), 0, st, (const double*)e->d_V, count, (const double*)e->d_w, e->d_part, e->n, e->P);
       GLX_HIP(hipGetLastError());
-      hipLaunchKernelGGL(eig_finish_kernel, dim3(eig_blocks(count, EIG_FIN_COLS)), dim3(EIG_FIN_THREADS), 0, st, (const double*)e->d_part, e->P, count, out,
+      hipLaunchKernelGGL(eig_finish_kernel, dim3(eig_blocks(count, FS_FIN_COLS)), dim3(FS_FIN_THREADS), 0, st, (const double*)e->d_part, e->P, count, out,
                          pass && alpha_slot ? 1 : 0, (const double*)h, alpha_slot);
       GLX_HIP(hipGetLastError());
     }
@@ -220,7 +198,7 @@ static int eig_orthogonalise(glx_eig* e, int count, int dst, double* alpha_slot,
       GLX_HIP(hipGetLastError());
     }
   }
-  hipLaunchKernelGGL(eig_finish_kernel, dim3(1), dim3(EIG_FIN_THREADS), 0, st, (const double*)e->d_part, e->P, 1, h, 2, (const double*)nullptr, beta_slot);
+  hipLaunchKernelGGL(eig_finish_kernel, dim3(1), dim3(FS_FIN_THREADS), 0, st, (const double*)e->d_part, e->P, 1, h, 2, (const double*)nullptr, beta_slot);
   GLX_HIP(hipGetLastError());
   hipLaunchKernelGGL(eig_scale_kernel, dim3(eig_blocks(e->n, 256)), dim3(256), 0, st, (const double*)e->d_w, (const double*)beta_slot,
                      e->d_V + (int64_t)dst * e->n, e->n);
@@ -255,7 +233,7 @@ extern "C" int glx_eig_create(int64_t n, const int64_t* row_ptr, const int32_t* 
   e->nnz = nnz;
   e->m = m;
   e->device = device;
-  e->P = eig_partials(n);
+  e->P = fs_partials(n);
   hipStream_t st = call.stream();
   int rc = GLX_OK;
   do {

@@ -9,16 +9,20 @@
 //
 // One Lanczos step j works on the columns 0 .. j, every operation rounded on its own (no fused multiply-add):
 //   1. t = A v_j, w = A t: each row adds its stored entries in order, from +0.0, of val[e] * x[col[e]];
-//   2. h_c = v_c . w for c = 0 .. j: rows [64 p, 64 p + 64) form partial p (rows past n count as +0.0), summed by the halving tree
-//      ck_tree64; the partials of a column are finished by 64 chains in ascending order and the tree over the chains (ck_finish);
+//   2. h_c = v_c . w for c = 0 .. j in the reduction order of fixed_sum.h: the 64 rows of a partial by fs_tree64 (fs_tree_dot), the
+//      partials of a column by fs_finish;
 //   3. w_i <- w_i - h_c * v_c[i] for c = 0, 1, .. j in that order, product and difference rounded separately;
 //   4. 2 and 3 once more, giving g; alpha_j = h_j + g_j, beta_j = sqrt(w . w) in the same reduction order, v_{j+1}[i] = w_i / beta_j.
 // Orthonormalising column j is 2 - 4 without the operator: w = v_j, the columns 0 .. j - 1, v_j <- w / sqrt(w . w).
 // The rotation V[:, :keep] <- V[:, :rows] Y adds, per element, the products V[i, c] * Y[c, q] over c = 0 .. rows - 1 in ascending
 // order from +0.0; then V[:, keep] <- V[:, rows].
 #pragma once
-#include "ck_plan.h"
+#include "fixed_sum.h"
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
 #include <cstring>
+#include <vector>
 
 static const int EIG_MAX_M = 513;          // widest basis: 2 * EIG_MAX_K + 1
 static const int EIG_MAX_K = 256;          // columns handed out at once at most
@@ -33,13 +37,10 @@ inline int64_t eig_basis_size(int64_t n, int64_t k) {
   return m < n ? m : n;
 }
 
-// partial sums of one column
-inline int64_t eig_partials(int64_t n) { return (n + CK_ROWS - 1) / CK_ROWS; }
-
 // device bytes of a solver object at its peak: the m + 1 basis columns, w and t, the CSR arrays, the partial sums of m + 1 columns
 // and the scalars.  The rotation works in place out of LDS: no scratch of the basis' size.
 inline int64_t eig_device_bytes(int64_t n, int64_t nnz, int64_t m) {
-  return (m + 1 + 2) * n * 8 + (n + 1) * 8 + nnz * 12 + eig_partials(n) * (m + 1) * 8 + (int64_t)EIG_MAX_M * EIG_MAX_M * 8 + 8 * (m + 1) * 8;
+  return (m + 1 + 2) * n * 8 + (n + 1) * 8 + nnz * 12 + fs_partials(n) * (m + 1) * 8 + (int64_t)EIG_MAX_M * EIG_MAX_M * 8 + 8 * (m + 1) * 8;
 }
 
 // 0, or a message in `msg` and: 1 sizes, 2 row pointers, 3 a column index out of range, 4 a row that is not canonical, 6 a value
@@ -99,23 +100,16 @@ inline void eig_h_spmv(int64_t n, const int64_t* row_ptr, const int32_t* col, co
   }
 }
 
-// h[c] = v_c . w for c < count; part: eig_partials(n) * count doubles of scratch
+// h[c] = v_c . w for c < count; part: fs_partials(n) * count doubles of scratch
 inline void eig_h_dots(int64_t n, const double* V, int count, const double* w, double* part, double* h) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
   if (count < 1) return;
-  const int64_t P = eig_partials(n);
-  double a[CK_ROWS];
+  const int64_t P = fs_partials(n);
   for (int64_t p = 0; p < P; ++p)
-    for (int c = 0; c < count; ++c) {
-      for (int r = 0; r < CK_ROWS; ++r) {
-        const int64_t i = p * CK_ROWS + r;
-        a[r] = i < n ? V[(int64_t)c * n + i] * w[i] : 0.0;
-      }
-      part[p * count + c] = ck_tree64(a);
-    }
-  ck_finish(part, P, count, h);
+    for (int c = 0; c < count; ++c) part[p * count + c] = fs_tree_dot(V + (int64_t)c * n, w, n, p);
+  fs_finish(part, P, count, h);
 }
 
 // w_i <- w_i - h[c] * v_c[i], c ascending
@@ -133,21 +127,15 @@ inline void eig_h_update(int64_t n, const double* V, int count, const double* h,
   }
 }
 
-// sqrt(w . w); part: eig_partials(n) doubles of scratch
+// sqrt(w . w); part: fs_partials(n) doubles of scratch
 inline double eig_h_norm(int64_t n, const double* w, double* part) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  const int64_t P = eig_partials(n);
-  double a[CK_ROWS], s;
-  for (int64_t p = 0; p < P; ++p) {
-    for (int r = 0; r < CK_ROWS; ++r) {
-      const int64_t i = p * CK_ROWS + r;
-      a[r] = i < n ? w[i] * w[i] : 0.0;
-    }
-    part[p] = ck_tree64(a);
-  }
-  ck_finish(part, P, 1, &s);
+  const int64_t P = fs_partials(n);
+  double s;
+  for (int64_t p = 0; p < P; ++p) part[p] = fs_tree_dot(w, w, n, p);
+  fs_finish(part, P, 1, &s);
   return std::sqrt(s);
 }
 
@@ -169,7 +157,7 @@ struct EigHost {
     V.assign((size_t)(m + 1) * n, 0.0);
     w.assign((size_t)n, 0.0);
     t.assign((size_t)n, 0.0);
-    part.assign((size_t)eig_partials(n) * (m + 1), 0.0);
+    part.assign((size_t)fs_partials(n) * (m + 1), 0.0);
     h.assign((size_t)m + 1, 0.0);
     g.assign((size_t)m + 1, 0.0);
   }

@@ -10,15 +10,15 @@
 // by one thread each in the order of j, the label decided and recorded where the step follows a projection, the fidelity term, X
 // scaled by the eigenvalue factors in place -- and then every thread adds b[r, c] * y[r, j] for the (c, j) it owns, row after row,
 // into registers: the chain of mmbo_plan.h.  The finishing kernel adds the partials of 16 values per workgroup in the fixed order of
-// ck_finish (64 chains, then the tree) and leaves the next Z.  No floating-point atomic, no grid-wide wait, nothing depends on which
-// workgroup ends first.  One last pass decides the final labels.
+// fs_finish (fixed_sum.h; fs_finish_cols of fixed_sum_device.h) and leaves the next Z.  No floating-point atomic, no grid-wide wait,
+// nothing depends on which workgroup ends first.  One last pass decides the final labels.
 //
 // Buffers come from the pool and are written before they are read; no launch sequence is captured.
 #include "glx_internal.h"
 #include "mmbo_plan.h"
+#include "fixed_sum_device.h"
 #include <vector>
 
-#define MMBO_FIN_THREADS (CK_CHAINS * MMBO_FIN_COLS)
 #define MMBO_OWN (MMBO_CAP / MMBO_THREADS)          // (c, j) pairs a thread of the pass owns at most
 
 // lab_in: read by MMBO_START; lab_out: written by MMBO_PROJECT and MMBO_LABELS; part (P, k m): not written by MMBO_LABELS
@@ -117,21 +117,13 @@ __global__ __launch_bounds__(MMBO_THREADS) void mmbo_pass_kernel(const double* _
   }
 }
 
-// Z[j] for the MMBO_FIN_COLS values of this workgroup: chain q adds the partials q, q + 64, .. in order, then the tree over the chains
-__global__ __launch_bounds__(MMBO_FIN_THREADS) void mmbo_finish_kernel(const double* __restrict__ part, int64_t P, int km, double* __restrict__ Z) {
+// Z[j] for the FS_FIN_COLS values of this workgroup, in the order of fs_finish
+__global__ __launch_bounds__(FS_FIN_THREADS) void mmbo_finish_kernel(const double* __restrict__ part, int64_t P, int km, double* __restrict__ Z) {
 #pragma clang fp contract(off)
-  __shared__ double s_a[MMBO_FIN_THREADS];
-  const int q = (int)threadIdx.x / MMBO_FIN_COLS, cc = (int)threadIdx.x % MMBO_FIN_COLS;
-  const int j = (int)blockIdx.x * MMBO_FIN_COLS + cc;
-  double a = 0.0;
-  if (j < km)
-    for (int64_t p = q; p < P; p += CK_CHAINS) a = a + part[p * km + j];
-  s_a[q * MMBO_FIN_COLS + cc] = a;
-  for (int h = CK_CHAINS / 2; h >= 1; h >>= 1) {
-    __syncthreads();
-    if (q < h) s_a[q * MMBO_FIN_COLS + cc] = s_a[q * MMBO_FIN_COLS + cc] + s_a[(q + h) * MMBO_FIN_COLS + cc];
-  }
-  if (q == 0 && j < km) Z[j] = s_a[cc];
+  __shared__ double s_a[FS_FIN_THREADS];
+  const int j = (int)blockIdx.x * FS_FIN_COLS + (int)threadIdx.x;          // (of the threads of chain 0)
+  const double s = fs_finish_cols(part, P, km, (int)blockIdx.x * FS_FIN_COLS, s_a);
+  if ((int)threadIdx.x < FS_FIN_COLS && j < km) Z[j] = s;
 }
 
 extern "C" int glx_mmbo_solve(int64_t n, int m, const double* X, const double* vals, const int32_t* lab0, int64_t ntrain, const int32_t* ind,
@@ -163,7 +155,7 @@ extern "C" int glx_mmbo_solve(int64_t n, int m, const double* X, const double* v
 
   const int sub = mmbo_sub_rows(k, m);
   const size_t lds = mmbo_lds_doubles(k, m, sub) * 8;          // 52 KiB at the most
-  const unsigned fin_blocks = (unsigned)((km + MMBO_FIN_COLS - 1) / MMBO_FIN_COLS);
+  const unsigned fin_blocks = (unsigned)((km + FS_FIN_COLS - 1) / FS_FIN_COLS);
   int64_t launches = 0;
   for (int64_t g = 0; g < T * Ns; ++g) {
     const int mode = mmbo_mode(g, Ns);
@@ -171,7 +163,7 @@ extern "C" int glx_mmbo_solve(int64_t n, int m, const double* X, const double* v
     hipLaunchKernelGGL(mmbo_pass_kernel, dim3((unsigned)P), dim3(MMBO_THREADS), lds, st, (const double*)d_x, (const double*)d_d,
                        (const int32_t*)d_tl, (const int32_t*)d_lab0, out, (const double*)d_z, d_part, n, m, k, sub, mode, plan.c0);
     GLX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mmbo_finish_kernel, dim3(fin_blocks), dim3(MMBO_FIN_THREADS), 0, st, (const double*)d_part, P, km, d_z);
+    hipLaunchKernelGGL(mmbo_finish_kernel, dim3(fin_blocks), dim3(FS_FIN_THREADS), 0, st, (const double*)d_part, P, km, d_z);
     GLX_HIP(hipGetLastError());
     launches += 2;
   }

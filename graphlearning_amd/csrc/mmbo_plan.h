@@ -18,20 +18,23 @@
 // pass decides the labels of outer iteration T.  u is never stored.
 //
 // The reduction order.  Rows [64 p, 64 p + 64) form partial p whatever k and m are.  Inside a partial every (c, j) is ONE CHAIN over the
-// partial's rows in ascending order from +0.0 -- not the halving tree of ck_tree64: a tree over 64 rows wants 64 k m doubles side by
-// side (2 MiB at the cap), a chain wants one register per (c, j).  Rows past n are not added.  The partials of a (c, j) are finished as
-// the centered-kernel learner's are (ck_finish of ck_plan.h): chain q of 64 adds the partials p = q, q + 64, .. in ascending order from
-// +0.0, then the halving tree a[r] += a[r + h], h = 32 .. 1, over the chains.  Nothing depends on which workgroup ends first.
+// partial's rows in ascending order from +0.0 -- not the halving tree of fs_tree64: a tree over 64 rows wants 64 k m doubles side by
+// side (2 MiB at the cap), a chain wants one register per (c, j).  Rows past n are not added.  The partials of a (c, j) are finished
+// in the order of fixed_sum.h (fs_finish).  Nothing depends on which workgroup ends first.
 //
 // Caps: k <= 256, m <= 256, k * m <= MMBO_CAP = 4096 (Z in LDS: 32 KiB and a pad), n * m, T * n and partials * k * m at most 2^31.
 #pragma once
-#include "ck_plan.h"
+#include "fixed_sum.h"
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <limits>
+#include <vector>
 
-static const int MMBO_ROWS = 64;              // rows per partial sum
+static const int MMBO_ROWS = FS_ROWS;         // rows per partial sum
 static const int MMBO_SUB_MIN = 8;            // rows a workgroup of the pass holds in LDS at a time, at least (mmbo_sub_rows)
 static const int MMBO_LDS_BYTES = 48 << 10;   // what the pass's LDS may take before the rows held at a time are halved
 static const int MMBO_THREADS = 256;          // threads of the pass
-static const int MMBO_FIN_COLS = 16;          // values a workgroup of the finishing kernel finishes (CK_CHAINS * MMBO_FIN_COLS threads)
 static const int MMBO_MAX_K = 256;
 static const int MMBO_MAX_M = 256;
 static const int MMBO_CAP = 4096;             // k * m at most
@@ -41,7 +44,7 @@ struct MmboPlan {
   std::vector<int32_t> tl;                    // (n) the training label of a vertex (the last one that lists it), -1 elsewhere
   std::vector<double> d;                      // (m) 1 / (1 + h * vals[j])
   double c0 = 0;                              // (dt / Ns) * mu
-  int64_t P = 0;                              // partials: ceil(n / MMBO_ROWS)
+  int64_t P = 0;                              // partials: fs_partials(n)
 };
 
 inline void mmbo_factors(int m, const double* vals, int64_t Ns, double dt, double mu, double* c0, double* d) {
@@ -74,7 +77,7 @@ inline int mmbo_validate(int64_t n, int m, const double* X, const double* vals, 
     snprintf(msg, cap, "dt=%g or mu=%g not finite", dt, mu);
     return 3;
   }
-  const int64_t P = (n + MMBO_ROWS - 1) / MMBO_ROWS;
+  const int64_t P = fs_partials(n);
   if (k > MMBO_MAX_K || m > MMBO_MAX_M || (int64_t)k * m > MMBO_CAP || n * (int64_t)m > (1ll << 31) || T * n > (1ll << 31) ||
       P * (int64_t)k * m > (1ll << 31)) {
     snprintf(msg, cap, "k=%d classes or m=%d columns (at most %d and %d), k * m = %d (at most %d), or n * m, T * n or partials * k * m above 2^31",
@@ -118,7 +121,7 @@ inline void mmbo_make_plan(int64_t n, int m, const double* vals, int64_t ntrain,
   mmbo_factors(m, vals, Ns, dt, mu, &P.c0, P.d.data());
   P.tl.assign((size_t)n, -1);
   for (int64_t q = 0; q < ntrain; ++q) P.tl[ind[q]] = lab[q];
-  P.P = (n + MMBO_ROWS - 1) / MMBO_ROWS;
+  P.P = fs_partials(n);
 }
 
 // LDS doubles of the pass with `sub` rows held at a time: Z with its rows padded to an odd length, the rows' X, the rows' u
@@ -231,7 +234,7 @@ inline void mmbo_host_reference(int64_t n, int m, const double* X, const double*
   for (int64_t g = 0; g < T * Ns; ++g) {
     const int mode = mmbo_mode(g, Ns);
     mmbo_host_pass(plan, n, m, k, X, mode, lab0, mode == MMBO_PROJECT ? hist + (g / Ns - 1) * n : nullptr, Z.data(), part.data(), &gap);
-    ck_finish(part.data(), plan.P, km, Z.data());
+    fs_finish(part.data(), plan.P, km, Z.data());
   }
   mmbo_host_pass(plan, n, m, k, X, MMBO_LABELS, nullptr, hist + (T - 1) * n, Z.data(), nullptr, &gap);
   for (int q = 0; q < km; ++q) Zlast[q] = Z[q];

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN_FILE = 'g18_ck.npz'
 # case -> (graph, classes)
 GOLDEN_CASES = {'blobs': ('blobs', 3), 'directed': ('directed', 3), 'ten': ('ten', 10), 'loops': ('loops', 3), 'tiny': ('tiny', 2)}
-ROWS = 64           # CK_ROWS and CK_CHAINS of ck_plan.h
+ROWS = 64           # FS_ROWS and FS_CHAINS of fixed_sum.h
 MAX_IT = 1 << 24
 
 

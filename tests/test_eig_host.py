@@ -285,7 +285,8 @@ def test_entry_points_are_declared():
     assert re.search(r'int glx_eig_create\(int64_t n, const int64_t\* row_ptr, const int32_t\* col, const double\* val, int m, int device,', text)
     with open(os.path.join(ROOT, 'graphlearning_amd', 'csrc', 'eig_plan.h')) as f:
         plan = f.read()
-    assert 'hip' not in re.sub(r'//.*', '', plan).lower() and '#include "ck_plan.h"' in plan       # no HIP header; ck's tree and chains are shared
+    assert 'hip' not in re.sub(r'//.*', '', plan).lower()                                          # no HIP header
+    assert '#include "fixed_sum.h"' in plan and '#include "ck_plan.h"' not in plan                 # the shared sum, not another learner's plan
     for name in ('set_column', 'orthonormalize', 'run', 'rotate', 'get_columns', 'close', '__enter__', '__exit__'):
         assert callable(getattr(_hip.Eig, name))
     assert callable(gl.graph.graph.eigen_decomp)

@@ -80,11 +80,13 @@ def test_golden_within_the_measured_bound(gl, gold, name):
 
 # seed, n, k, hub, directed, rows without entries: every n of {1, 2, 63, 64, 65, 257, 1000} (one partial exactly: 1 .. 64; n no multiple
 # of the 64 rows of a partial: 65, 257, 1000), every k of {1, 2, 3, 10, 17, 64, 65, 256} (one column tile up to 16, tiles of unequal width
-# at 17 and 65, sixteen tiles at 256); the seeds are ones whose
+# at 17 and 65, sixteen tiles at 256), and n = 4097: 65 partials, so that chain 0 of the finishing kernel holds two of them, with one
+# round of its 16 columns (k = 2: four sums) and three (k = 17: 34 sums); the seeds are ones whose
 # problem stops within a few hundred iterations at tol = 1e-6
 SHAPES = [(10, 1, 1, 0, False, 0), (11, 2, 2, 0, False, 0), (12, 63, 3, 0, False, 0), (13, 64, 10, 0, False, 0), (14, 65, 17, 0, False, 0),
           (100, 257, 64, 0, False, 2), (16, 257, 65, 0, False, 0), (40, 1000, 256, 0, False, 0), (41, 1000, 1, 0, False, 3),
-          (19, 1000, 2, 0, False, 0), (100, 1000, 10, 0, False, 0), (5, 64, 10, 0, True, 0), (107, 1000, 17, 0, True, 2)]
+          (19, 1000, 2, 0, False, 0), (100, 1000, 10, 0, False, 0), (5, 64, 10, 0, True, 0), (107, 1000, 17, 0, True, 2),
+          (36, 4097, 2, 0, False, 0), (17, 4097, 17, 0, False, 0)]
 
 
 @pytest.mark.parametrize('seed,n,k,hub,directed,lonely', SHAPES)

@@ -119,6 +119,33 @@ def test_operations_bit_for_bit(gl, lib, n):
         host.close()
 
 
+def test_sums_of_65_partials_bit_for_bit(gl, lib):
+    """n = 4097: 65 partials, so chain 0 of the finishing kernel adds two of them (the stride of 64 between the partials of a chain).
+    j covers 1, 2, 16, 17 and 18 columns: one and two workgroups of the finishing kernel."""
+    n, m = 4097, 20
+    A = operation_matrix(n)
+    dev, host = both(gl, lib, A, m)
+    try:
+        rng = np.random.default_rng(n)
+        for j in range(m + 1):
+            x = rng.uniform(-1, 1, size=n)
+            dev.set_column(j, x)
+            host.set_column(j, x)
+        for j in (0, 1, 15, 16, 17):
+            (a, b), (ha, hb) = dev.run(j, j + 1), host.run(j, j + 1)
+            print(n, 'run', j, 'alpha', a, 'beta', b)
+            assert ref.same_bits(a, ha) and ref.same_bits(b, hb) and np.all(np.isfinite(a)) and np.all(np.isfinite(b)), j
+            assert ref.same_bits(dev.get_columns(j + 1, j + 2), host.get_columns(j + 1, j + 2)), j
+        for j in (0, 1, 15, 16, 17):
+            norm, hnorm = dev.orthonormalize(j), host.orthonormalize(j)
+            assert norm == hnorm and np.isfinite(norm), j
+            assert ref.same_bits(dev.get_columns(j, j + 1), host.get_columns(j, j + 1)), j
+        assert same_basis(dev, host, m)
+    finally:
+        dev.close()
+        host.close()
+
+
 def test_refusals_of_the_object(gl, lib):
     from graphlearning_amd import _hip
     A = operation_matrix(65)

@@ -15,6 +15,7 @@ from scipy import sparse
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import eig_ref                      # noqa: E402
+import fixed_sum_ref                # noqa: E402
 import mmbo_ref as ref              # noqa: E402
 import graphlearning_amd as gl      # noqa: E402
 from graphlearning_amd import _hip  # noqa: E402
@@ -109,14 +110,7 @@ def test_host_reference_on_seeded_shapes(lib):
             part = np.zeros((P, k, m))
             for i in range(n):
                 part[i // 64] = part[i // 64] + b[i][:, None] * Y[i][None, :]
-            chains = np.zeros((64, k, m))
-            for p in range(P):
-                chains[p % 64] = chains[p % 64] + part[p]
-            hh = 32
-            while hh >= 1:
-                chains[:hh] = chains[:hh] + chains[hh:2 * hh]
-                hh //= 2
-            Zc = chains[0]
+            Zc = fixed_sum_ref.finish(part)
         assert np.array_equal(hist, np.array(want)) and eig_ref.same_bits(Z, Zc), (n, m, k)
 
 
@@ -266,7 +260,8 @@ def test_entry_point_is_declared():
     assert getattr(_hip.load(), 'glx_mmbo_solve') is not None
     with open(os.path.join(ROOT, 'graphlearning_amd', 'csrc', 'mmbo_plan.h')) as f:
         plan = f.read()
-    assert '#include <hip' not in plan and 'glx_internal.h' not in plan                # host only
+    assert 'hip' not in re.sub(r'//.*', '', plan).lower() and 'glx_internal.h' not in plan                # host only
+    assert '#include "fixed_sum.h"' in plan and '#include "ck_plan.h"' not in plan                       # the shared sum, not another learner's plan
     with open(os.path.join(ROOT, 'graphlearning_amd', 'csrc', 'mmbo.hip')) as f:
         kern = f.read()
     assert not re.search(r'atomicAdd|unsafeAtomicAdd|cooperative_groups|hipMemsetAsync|__builtin_amdgcn_mfma|fma\(', kern)
