@@ -7,10 +7,7 @@
 // history in chunks; kernels of iterations past convergence exit at once (same trick as the sweep's
 // stop column).  The tolerance mode (GLX_CG_TREE) lives in cg_fused.hip.
 #include "cg_internal.h"
-#include <map>
 #include <string.h>
-#include <algorithm>
-#include <vector>
 #include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -19,7 +16,6 @@ template <typename T> struct V4Of;
 template <> struct V4Of<float> { typedef f32x4 type; };
 template <> struct V4Of<double> { typedef f64x4 type; };
 
-static const int CG_CHUNK = 8;
 static const int UPD_ROWS_PER_BLOCK = 256;
 
 // x += alpha p ; r -= alpha Ap ; partial[b][c] = sum_rows r^2           (utils.py:525-527)
@@ -378,72 +374,6 @@ __global__ __launch_bounds__(256) void cg_pw_tree_kernel(PwPlan pw, CgScalars sc
   }
 }
 
-// host side of the plan: the recursion of DOUBLE_pairwise_sum on (offset, n)
-struct PwHost {
-  std::vector<int64_t> leaf_off;
-  std::vector<int32_t> leaf_len, node_l, node_r, node_h, level_start;
-  // returns a provisional id: leaves >= 0, internal nodes as -(index + 1)
-  int build(int64_t off, int64_t n, int* height) {
-    if (n <= 128) {
-      leaf_off.push_back(off);
-      leaf_len.push_back((int32_t)n);
-      *height = 0;
-      return (int)leaf_off.size() - 1;
-    }
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
-    int hl, hr;
-    const int l = build(off, n2, &hl);
-    const int r = build(off + n2, n - n2, &hr);
-    *height = std::max(hl, hr) + 1;
-    node_l.push_back(l);
-    node_r.push_back(r);
-    node_h.push_back(*height);
-    return -(int)node_l.size();
-  }
-  // numpy hands a contiguous 1-D reduction to the pairwise routine in pieces of its buffer size
-  // (8192 elements) and adds the pieces' sums one after another: ((c0 + c1) + c2) + ...
-  void build_chunked(int64_t n) {
-    const int64_t NPY_BUFSIZE = 8192;
-    int h, hacc = 0;
-    int acc = build(0, std::min(n, NPY_BUFSIZE), &hacc);
-    for (int64_t off = NPY_BUFSIZE; off < n; off += NPY_BUFSIZE) {
-      const int c = build(off, std::min(NPY_BUFSIZE, n - off), &h);
-      hacc = std::max(hacc, h) + 1;
-      node_l.push_back(acc);
-      node_r.push_back(c);
-      node_h.push_back(hacc);
-      acc = -(int)node_l.size();
-    }
-  }
-  void finish() {   // order the internal nodes by height (stable: children always precede parents) and renumber
-    const int ni = (int)node_l.size(), nl = (int)leaf_off.size();
-    std::vector<int> order(ni);
-    for (int q = 0; q < ni; ++q) order[q] = q;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return node_h[x] < node_h[y]; });
-    std::vector<int> newpos(ni);
-    for (int q = 0; q < ni; ++q) newpos[order[q]] = q;
-    auto remap = [&](int id) { return id >= 0 ? id : nl + newpos[-id - 1]; };
-    std::vector<int32_t> l2(ni), r2(ni);
-    int maxh = 0;
-    for (int q = 0; q < ni; ++q) {
-      l2[q] = remap(node_l[order[q]]);
-      r2[q] = remap(node_r[order[q]]);
-      maxh = std::max(maxh, (int)node_h[order[q]]);
-    }
-    level_start.assign(maxh + 1, 0);
-    for (int q = 0; q < ni; ++q) level_start[node_h[order[q]]]++;   // counts per height h >= 1 at index h
-    // prefix: level_start[h-1] = first internal node of height h
-    std::vector<int32_t> ls(maxh + 1, 0);
-    int acc = 0;
-    for (int h = 1; h <= maxh; ++h) { ls[h - 1] = acc; acc += level_start[h]; }
-    ls[maxh] = acc;
-    level_start = ls;
-    node_l = l2;
-    node_r = r2;
-  }
-};
-
 // the ring of CG_CHUNK + 1 history rows: row 0 and the last row = 1 (utils.py:519: err = 1 in front of the loop; every chunk starts by
 // copying the last row to row 0), the others 0 (= stopped)
 __global__ void cg_set_err0(double* err_hist, int64_t n, int stride, int last_row) {
@@ -483,88 +413,131 @@ __global__ __launch_bounds__(256) void cg_scatter_rows_kernel(T* __restrict__ re
   rec[(size_t)(inv ? inv[row] : row) * ld + c] = vals[i];
 }
 
-template <typename T>
-static int cg_run(glx_graph* A, const void* B, void* X, int C, int Cg, double tol, int64_t max_iter, int* iters_out,
-                  double* err_out, int flags, const int32_t* mask_rows, const int32_t* mask_ptr, const CgRhsRows& rr) {
-  if (flags & GLX_CG_TREE)     // tolerance mode: cg_fused.hip (deterministic, not bit-identical to numpy's chains)
-    return glx_cg_run_fused(A, B, X, C, Cg, tol, max_iter, iters_out, err_out, flags, mask_rows, mask_ptr, rr);
-  const bool np1d = (flags & 1) && C == 1;   // caller passed a 1-D right-hand side: numpy's pairwise reductions
-  const int ngroups = C / Cg;
-  const int stride = ngroups + 1;
-  const int64_t n = A->n_rows;
-  const int dtype = A->dtype;
-  RecLayout L;
-  int rc = glx_make_layout(C, dtype, false, &L);
+// ---- the stages both modes share (cg_internal.h) -----------------------------------------------------------------------------------
+int cg_open(CgSolve& c, bool relaxed, CgLimits limits, const int32_t* mask_rows, const int32_t* mask_ptr) {
+  int rc = glx_make_layout(c.s.C, c.dtype, false, &c.L);
   if (rc) return rc;
-  SellPlan* plan = nullptr;
-  rc = glx_graph_plan(A, L.G, &plan);
+  rc = glx_graph_plan(c.A, c.L.G, &c.plan, relaxed);
   if (rc) return rc;
-  const size_t es = L.esize;
-  const int ncols = L.nvec * 4;
-  GLX_CHECK(ncols <= 256, GLX_EUNSUPPORTED, "glx_cg_multi: C=%d too wide for the column reducer", C);
-  GLX_CHECK(Cg <= 128, GLX_EUNSUPPORTED, "glx_cg_multi: %d columns per system too wide for the reference-order reducer", Cg);
-  GLX_CHECK(256 / (L.ld / 4) >= 1, GLX_EUNSUPPORTED, "glx_cg_multi: record too wide");
-  const int64_t nb_spmm = std::max<int64_t>(glx_spmm_blocks(plan), 1);
-  const int64_t nb_upd = std::max<int64_t>((n + UPD_ROWS_PER_BLOCK - 1) / UPD_ROWS_PER_BLOCK, 1);
-  const int64_t hist_cap = CG_CHUNK + 1;       // a ring: row 0 = what the chunk's first iteration tests, rows 1 .. CG_CHUNK = what its iterations leave
-  GLX_CHECK(max_iter < (1ll << 24), GLX_EUNSUPPORTED, "glx_cg_multi: max_iter %lld exceeds the supported 2^24-1", (long long)max_iter);
-  GLX_CHECK(n < (1ll << 27), GLX_EUNSUPPORTED, "glx_cg_multi: %lld rows exceed the reference-order reducer's 32-bit offsets", (long long)n);
-
-  // reference-order reducer: one wavefront per 4 columns; the product array is blocked the same way
-  const int prod_sc = 4;
-  const unsigned seq_grid = (unsigned)(ncols / 4);
-  if (!A->cg_ws) A->cg_ws = new CgBufs();
-  CgBufs& b = *(CgBufs*)A->cg_ws;
-  const size_t recb = std::max<size_t>((size_t)n * L.ld * es, 64);
+  c.s.ncols = c.L.nvec * 4;
+  c.s.ld = c.L.ld;
+  c.s.nmask = (mask_rows && mask_ptr) ? mask_ptr[c.s.ngroups] : 0;
+  char msg[192];
+  rc = limits(c.s, msg, sizeof msg);
+  GLX_CHECK(!rc, rc, "%s", msg);
+  c.nb_spmm = std::max<int64_t>(glx_spmm_blocks(c.plan), 1);
+  CgBufs& b = c.b;
+  c.recb = std::max<size_t>((size_t)c.s.n * c.L.ld * c.L.esize, 64);
+  c.denseb = (size_t)c.s.n * c.s.C * c.L.esize;
   if (!b.stream) GLX_HIP(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
-  CG_NEED(b.x, recb);
-  CG_NEED(b.r, recb);
-  CG_NEED(b.p, recb);
-  CG_NEED(b.ap, recb);
-  CG_NEED(b.dense, (size_t)n * C * es);
-  CG_NEED(b.part_dot, (size_t)nb_spmm * ncols * 8);
-  CG_NEED(b.part_rs, (size_t)nb_upd * ncols * 8);
-  CG_NEED(b.scal, (size_t)3 * ncols * 8);
-  CG_NEED(b.err_hist, (size_t)hist_cap * stride * 8);
-  CG_NEED(b.prod, (size_t)ncols * n * 8);
-  // the two reference-order chains per iteration: walked row by row (cg_seqsum_dpp_kernel, 2.4 ns per row) or in block form
-  // (cg_seqsum.hip: integer block sums confirmed by the exact state; same bits) -- the block form from 8192 rows on
-  SsWork ssw;
-  memset(&ssw, 0, sizeof(ssw));
-  ssw.nchunks = glx_seqsum_chunks(n);
-  const bool ss_blocks = !np1d && !(flags & GLX_CG_CHAIN) && ssw.nchunks <= glx_seqsum_max_chunks() && n >= 1 &&
-                         glx_seqsum_rec_bytes(ncols, ssw.nchunks) <= ((size_t)1 << 30) &&      // (hundreds of columns x millions of rows: the chain)
-                         ((flags & GLX_CG_BLOCKS) || n >= 8192);
-  if (ss_blocks) {
-    rc = glx_seqsum_prepare();
-    if (rc) return rc;
-    CG_NEED(b.ss_bsum, glx_seqsum_sum_doubles(ncols, ssw.nchunks, 0) * 8);
-    CG_NEED(b.ss_csum, glx_seqsum_sum_doubles(ncols, ssw.nchunks, 1) * 8);
-    CG_NEED(b.ss_rec, glx_seqsum_rec_bytes(ncols, ssw.nchunks));
-    CG_NEED(b.ss_mask, (size_t)ncols * ssw.nchunks * 16);      // a byte per group of 4 blocks
-    CG_NEED(b.ss_stats, 128);
-    ssw.rec = b.ss_rec;
-    ssw.bsum = b.ss_bsum;
-    ssw.csum = b.ss_csum;
-    ssw.mask = b.ss_mask;
-    ssw.stats = b.ss_stats;
-    { int rc_ = b.need_host(&b.h_ss, 256); if (rc_) return rc_; }
-    memset(b.h_ss, 0, 256);
+  c.st = b.stream;
+  CG_NEED(b.x, c.recb);
+  CG_NEED(b.r, c.recb);
+  CG_NEED(b.p, c.recb);
+  CG_NEED(b.ap, c.recb);
+  CG_NEED(b.dense, c.denseb);
+  CG_NEED(b.scal, (size_t)3 * c.s.ncols * 8);
+  memset(&c.a, 0, sizeof(c.a));
+  c.a.plan = c.plan;
+  c.a.L = c.L;
+  c.a.dtype = c.dtype;
+  c.a.xin = b.p;
+  c.a.xout = b.ap;
+  c.a.n_rows = c.s.n;
+  c.a.exit_tol = c.tol;
+  c.a.act_cg = c.s.Cg;
+  c.a.act_c = c.s.C;
+  return GLX_OK;
+}
+
+int cg_load_dense(CgSolve& c, const void* host, void* rec) {
+  GLX_UP(glx_upload(c.b.dense, host, c.denseb, c.st, __func__));
+  return glx_pack_records(c.b.dense, rec, c.s.n, c.L, c.dtype, nullptr, c.st, c.A->d_perm);
+}
+
+int cg_finish(CgSolve& c, void* X, const double* scale, int* iters_out, double* err_out) {
+  CgBufs& b = c.b;
+  const int rc = scale ? glx_cg_unpack_scaled(c.dtype, b.x, b.dense, c.s.n, c.L, c.A->d_perm, scale, c.st)
+                       : glx_unpack_records(b.x, b.dense, c.s.n, c.L, c.dtype, c.st, c.A->d_perm);
+  if (rc) return rc;
+  GLX_UP(glx_download(X, b.dense, c.denseb, c.st, __func__));
+  GLX_HIP(hipStreamSynchronize(c.st));
+  for (int g = 0; g < c.s.ngroups; ++g) {
+    if (iters_out) iters_out[g] = (int)c.stop.iters[g];
+    if (err_out) err_out[g] = c.stop.err[g];
   }
-  // Per kind of reduction (0: p.Ap, 1: r.r) the form is re-decided whenever the host looks at the residual history: the block
-  // form costs about a microsecond per block that is not a plain same-binade one (a lone wavefront issues an instruction every
-  // four cycles), the chain 2.4 ns per row -- products that cancel (the singular Poisson system on separate clusters: p.Ap
-  // changes sign from row to row) are cheaper row by row.  Same bits either way, so switching in mid-solve changes nothing but time.
-  bool blocks_now[2] = {ss_blocks, ss_blocks};
-  const bool blocks_forced = (flags & GLX_CG_BLOCKS) != 0;
-  unsigned long long ss_seen[2][3] = {{0, 0, 0}, {0, 0, 0}};
+  return GLX_OK;
+}
+
+// ---- the reference-order solve -----------------------------------------------------------------------------------------------------
+template <typename T>
+struct CgExact : CgSolve {
+  using CgSolve::CgSolve;
+  static constexpr int prod_sc = 4;   // reference-order reducer: one wavefront per 4 columns; the product array is blocked the same way
+  bool np1d = false;              // caller passed a 1-D right-hand side: numpy's pairwise reductions
+  bool ss_blocks = false, use_graphs = true;
+  CgForms forms{false, false};
+  int64_t nb_upd = 1;
+  unsigned seq_grid = 1, pgrid = 1, pw_grid = 1, mask_grid = 0;
+  SsWork ssw;
   PwPlan pw;
-  memset(&pw, 0, sizeof(pw));
-  unsigned pw_grid = 1;
-  if (np1d) {   // numpy's pairwise-summation tree for n elements (depends on n only: kept with the buffers)
-    if (b.pw_n != n) {
+  CgScalars sc;
+  T *x = nullptr, *r = nullptr, *p = nullptr, *ap = nullptr;
+  const dim3 blk = dim3(256);
+
+  int open(const int32_t* mask_rows, const int32_t* mask_ptr) {
+    GLX_UP(cg_open(*this, false, cg_exact_limits, mask_rows, mask_ptr));
+    np1d = (flags & GLX_CG_NP1D) && s.C == 1;
+    use_graphs = !(flags & GLX_CG_EAGER);
+    nb_upd = std::max<int64_t>((s.n + UPD_ROWS_PER_BLOCK - 1) / UPD_ROWS_PER_BLOCK, 1);
+    seq_grid = (unsigned)(s.ncols / 4);
+    pgrid = (unsigned)std::max<int64_t>(((int64_t)s.n * (L.ld / 4) + 255) / 256, 1);
+    CG_NEED(b.part_dot, (size_t)nb_spmm * s.ncols * 8);
+    CG_NEED(b.part_rs, (size_t)nb_upd * s.ncols * 8);
+    // the history is a ring: row 0 = what the chunk's first iteration tests, rows 1 .. CG_CHUNK = what its iterations leave
+    CG_NEED(b.err_hist, (size_t)(CG_CHUNK + 1) * stride * 8);
+    CG_NEED(b.prod, (size_t)s.ncols * s.n * 8);
+    CG_NEED_HOST(b.h_err, (size_t)2 * (CG_CHUNK + 1) * stride * 8);      // two chunks in flight
+    for (int q = 0; q < 2; ++q)
+      if (!b.e_ev[q]) GLX_HIP(hipEventCreateWithFlags(&b.e_ev[q], hipEventDisableTiming));
+    sc = CgScalars{b.scal, b.scal + s.ncols, b.scal + 2 * s.ncols, b.err_hist, stride, s.ngroups, s.Cg, s.C};   // rsold, alpha, beta
+    x = (T*)b.x;
+    r = (T*)b.r;
+    p = (T*)b.p;
+    ap = (T*)b.ap;
+    a.dot_partial = b.part_dot;   // the fused dot also carries the kernel's early-exit hook
+    a.prod_out = b.prod;
+    a.perm = A->d_perm;
+    a.prod_sc = prod_sc;
+    return GLX_OK;
+  }
+
+  // the first decision for the block form of the two chains (cg_plan.h), and its buffers
+  int block_form_ready() {
+    memset(&ssw, 0, sizeof(ssw));
+    ssw.nchunks = glx_seqsum_chunks(s.n);
+    ss_blocks = cg_first_blocks(s.n, flags, np1d, ssw.nchunks, glx_seqsum_max_chunks(), glx_seqsum_rec_bytes(s.ncols, ssw.nchunks));
+    forms = CgForms(ss_blocks, (flags & GLX_CG_BLOCKS) != 0);
+    if (!ss_blocks) return GLX_OK;
+    GLX_UP(glx_seqsum_prepare());
+    CG_NEED(b.ss_bsum, glx_seqsum_sum_doubles(s.ncols, ssw.nchunks, 0) * 8);
+    CG_NEED(b.ss_csum, glx_seqsum_sum_doubles(s.ncols, ssw.nchunks, 1) * 8);
+    CG_NEED(b.ss_rec, glx_seqsum_rec_bytes(s.ncols, ssw.nchunks));
+    CG_NEED(b.ss_mask, (size_t)s.ncols * ssw.nchunks * 16);      // a byte per group of 4 blocks
+    CG_NEED(b.ss_stats, 128);
+    ssw = SsWork{b.ss_rec, b.ss_bsum, b.ss_csum, b.ss_mask, b.ss_stats, ssw.nchunks};
+    CG_NEED_HOST(b.h_ss, 256);
+    memset(b.h_ss, 0, 256);
+    return GLX_OK;
+  }
+
+  // numpy's pairwise-summation tree for n elements on the device (depends on n only: kept with the buffers)
+  int pairwise_plan_ready() {
+    memset(&pw, 0, sizeof(pw));
+    if (!np1d) return GLX_OK;
+    if (b.pw_n != s.n) {
       PwHost ph;
-      ph.build_chunked(n);
+      ph.build_chunked(s.n);
       ph.finish();
       const size_t nl = ph.leaf_off.size(), ni = ph.node_l.size();
       CG_NEED(b.pw_off, nl * 8);
@@ -580,312 +553,205 @@ static int cg_run(glx_graph* A, const void* B, void* X, int C, int Cg, double to
         GLX_UP(glx_upload_sync(b.pw_r, ph.node_r.data(), ni * 4, __func__));
       }
       if (!ph.level_start.empty()) GLX_UP(glx_upload_sync(b.pw_ls, ph.level_start.data(), ph.level_start.size() * 4, __func__));
-      b.pw.leaf_off = b.pw_off;
-      b.pw.leaf_len = b.pw_len;
-      b.pw.node_l = b.pw_l;
-      b.pw.node_r = b.pw_r;
-      b.pw.level_start = b.pw_ls;
-      b.pw.vals = b.pw_vals;
-      b.pw.nleaves = (int)nl;
-      b.pw.ninternal = (int)ni;
-      b.pw.nlevels = ph.level_start.empty() ? 0 : (int)ph.level_start.size() - 1;
+      const int nlevels = ph.level_start.empty() ? 0 : (int)ph.level_start.size() - 1;
+      b.pw = PwPlan{b.pw_off, b.pw_len, b.pw_l, b.pw_r, b.pw_ls, b.pw_vals, (int)nl, (int)ni, nlevels};
       b.pw_grid = (unsigned)((nl + 255) / 256);
-      b.pw_n = n;
+      b.pw_n = s.n;
     }
     pw = b.pw;
     pw_grid = b.pw_grid;
+    return GLX_OK;
   }
-  { int rc_ = b.need_host(&b.h_err, (size_t)2 * (CG_CHUNK + 1) * stride * 8); if (rc_) return rc_; }      // two chunks in flight
-  CgScalars sc;
-  sc.rsold = b.scal;
-  sc.alpha = b.scal + ncols;
-  sc.beta = b.scal + 2 * ncols;
-  sc.err_hist = b.err_hist;
-  sc.stride = stride;
-  sc.ngroups = ngroups;
-  sc.Cg = Cg;
-  sc.C = C;
-  hipStream_t st = b.stream;
-  const dim3 blk(256);
-  T* x = (T*)b.x;
-  T* r = (T*)b.r;
-  T* p = (T*)b.p;
-  T* ap = (T*)b.ap;
 
-  hipLaunchKernelGGL(cg_set_err0, dim3((unsigned)((hist_cap * stride + 255) / 256)), blk, 0, st, b.err_hist, hist_cap * stride, stride, CG_CHUNK);
-  GLX_HIP(hipGetLastError());
-  if (flags & GLX_CG_X0) {   // X holds x0 on entry; B is the caller's r0 = b - A@x0 (utils.py:510-514)
-    GLX_UP(glx_upload(b.dense, X, (size_t)n * C * es, st, __func__));
-    rc = glx_pack_records(b.dense, b.x, n, L, dtype, nullptr, st, A->d_perm);
-    if (rc) return rc;
-  } else {
-    GLX_HIP(hipMemsetAsync(b.x, 0, recb, st));
-  }
-  GLX_HIP(hipMemsetAsync(b.ap, 0, recb, st));
-  GLX_HIP(hipMemsetAsync(b.part_dot, 0, nb_spmm * ncols * 8, st));
-  GLX_HIP(hipMemsetAsync(b.scal, 0, 3 * ncols * 8, st));
-  if (rr.rows) {            // the nonzero rows only (ssl.laplace: the neighbours of the labelled vertices)
-    GLX_HIP(hipMemsetAsync(b.r, 0, recb, st));
-    if (rr.nb > 0) {
-      CG_NEED(b.rhs_rows, (size_t)rr.nb * 4);
-      GLX_UP(glx_upload(b.rhs_rows, rr.rows, (size_t)rr.nb * 4, st, __func__));
-      GLX_UP(glx_upload(b.dense, rr.vals, (size_t)rr.nb * C * es, st, __func__));
-      hipLaunchKernelGGL((cg_scatter_rows_kernel<T>), dim3((unsigned)((rr.nb * C + 255) / 256)), dim3(256), 0, st, (T*)b.r, L.ld, C,
-                         (const int32_t*)b.rhs_rows, (const T*)b.dense, rr.nb, (const int32_t*)A->d_inv);
-      GLX_HIP(hipGetLastError());
+  // one column reduction of iteration `i` (MODE as cg_seqsum_dpp_kernel's): numpy's pairwise tree, the block form or the chain
+  template <int MODE> int reduce(int i, bool blocks) {
+    if (np1d) {
+      hipLaunchKernelGGL(cg_pw_leaf_kernel, dim3(pw_grid), dim3(256), 0, st, (const double*)b.prod, prod_sc, pw, sc, i, tol, MODE);
+      hipLaunchKernelGGL(cg_pw_tree_kernel<MODE>, dim3(1), dim3(256), 0, st, pw, sc, i, tol);
+    } else if (blocks) {
+      GLX_UP(glx_seqsum_run(MODE, b.prod, s.n, s.ncols, s.C, sc, i, tol, ssw, st));
+    } else {
+      hipLaunchKernelGGL(cg_seqsum_dpp_kernel<MODE>, dim3(seq_grid), dim3(64), 0, st, (const double*)b.prod, s.n, s.ncols, s.C, sc, i, tol);
     }
-  } else {
-    GLX_UP(glx_upload(b.dense, B, (size_t)n * C * es, st, __func__));
-    rc = glx_pack_records(b.dense, b.r, n, L, dtype, nullptr, st, A->d_perm);   // r = b - A@0 = b (utils.py:514)
-    if (rc) return rc;
+    GLX_HIP(hipGetLastError());
+    return GLX_OK;
   }
-  if (rr.out_scale) {
-    CG_NEED(b.out_scale, (size_t)n * 8);
-    GLX_UP(glx_upload(b.out_scale, rr.out_scale, (size_t)n * 8, st, __func__));
-  }
-  GLX_HIP(hipMemcpyAsync(b.p, b.r, recb, hipMemcpyDeviceToDevice, st));   // p = r.copy() (utils.py:516)
-  hipLaunchKernelGGL((cg_update_kernel<T, 1>), dim3((unsigned)nb_upd), blk, 0, st, x, r, (const T*)p, (const T*)ap,
-                     (const double*)sc.alpha, b.part_rs, n, L.ld, L.nvec, sc, 1, tol, b.prod, prod_sc, (const int32_t*)A->d_perm);
-  GLX_HIP(hipGetLastError());
-  if (np1d)
-    {
-      hipLaunchKernelGGL(cg_pw_leaf_kernel, dim3(pw_grid), dim3(256), 0, st, (const double*)b.prod, prod_sc, pw, sc, 0, tol, 2);
-      hipLaunchKernelGGL(cg_pw_tree_kernel<2>, dim3(1), dim3(256), 0, st, pw, sc, 0, tol);
-    }
-  else if (ss_blocks) {
-    GLX_HIP(hipMemsetAsync(b.ss_stats, 0, 128, st));
-    rc = glx_seqsum_run(2, b.prod, n, ncols, C, sc, 0, tol, ssw, st);
-    if (rc) return rc;
-  } else
-    hipLaunchKernelGGL(cg_seqsum_dpp_kernel<2>, dim3(seq_grid), dim3(64), 0, st, (const double*)b.prod, n, ncols, C, sc, 0, tol);
-  GLX_HIP(hipGetLastError());
 
-  SweepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.plan = plan;
-  a.L = L;
-  a.dtype = dtype;
-  a.xin = b.p;
-  a.xout = b.ap;
-  a.dot_partial = b.part_dot;   // the fused dot also carries the kernel's early-exit hook
-  a.n_rows = n;
-  a.exit_tol = tol;
-  a.prod_out = b.prod;
-  a.perm = A->d_perm;
-  a.act_cg = Cg;
-  a.act_c = C;
-  a.prod_sc = prod_sc;
-  // Dirichlet rows per group (caller row numbers -> record indices)
-  unsigned mask_grid = 0;
-  if (mask_rows && mask_ptr && mask_ptr[ngroups] > 0) {
-    const int total = mask_ptr[ngroups];
+  // x = x0 or 0, r = p = b (dense, or its nonzero rows), rsold = sum r*r (utils.py:510-519)
+  int load_problem(const void* B, const void* X) {
+    const int64_t hist = (int64_t)(CG_CHUNK + 1) * stride;
+    hipLaunchKernelGGL(cg_set_err0, dim3((unsigned)((hist + 255) / 256)), blk, 0, st, b.err_hist, hist, stride, CG_CHUNK);
+    GLX_HIP(hipGetLastError());
+    if (flags & GLX_CG_X0)    // X holds x0 on entry; B is the caller's r0 = b - A@x0 (utils.py:510-514)
+      GLX_UP(cg_load_dense(*this, X, b.x));
+    else
+      GLX_HIP(hipMemsetAsync(b.x, 0, recb, st));
+    GLX_HIP(hipMemsetAsync(b.ap, 0, recb, st));
+    GLX_HIP(hipMemsetAsync(b.part_dot, 0, nb_spmm * s.ncols * 8, st));
+    GLX_HIP(hipMemsetAsync(b.scal, 0, 3 * s.ncols * 8, st));
+    if (rr.rows) {            // the nonzero rows only (ssl.laplace: the neighbours of the labelled vertices)
+      GLX_HIP(hipMemsetAsync(b.r, 0, recb, st));
+      if (rr.nb > 0) {
+        CG_NEED(b.rhs_rows, (size_t)rr.nb * 4);
+        GLX_UP(glx_upload(b.rhs_rows, rr.rows, (size_t)rr.nb * 4, st, __func__));
+        GLX_UP(glx_upload(b.dense, rr.vals, (size_t)rr.nb * s.C * L.esize, st, __func__));
+        hipLaunchKernelGGL((cg_scatter_rows_kernel<T>), dim3((unsigned)((rr.nb * s.C + 255) / 256)), dim3(256), 0, st, r, L.ld, s.C,
+                           (const int32_t*)b.rhs_rows, (const T*)b.dense, rr.nb, (const int32_t*)A->d_inv);
+        GLX_HIP(hipGetLastError());
+      }
+    } else {
+      GLX_UP(cg_load_dense(*this, B, b.r));   // r = b - A@0 = b (utils.py:514)
+    }
+    if (rr.out_scale) {
+      CG_NEED(b.out_scale, (size_t)s.n * 8);
+      GLX_UP(glx_upload(b.out_scale, rr.out_scale, (size_t)s.n * 8, st, __func__));
+    }
+    GLX_HIP(hipMemcpyAsync(b.p, b.r, recb, hipMemcpyDeviceToDevice, st));   // p = r.copy() (utils.py:516)
+    hipLaunchKernelGGL((cg_update_kernel<T, 1>), dim3((unsigned)nb_upd), blk, 0, st, x, r, (const T*)p, (const T*)ap,
+                       (const double*)sc.alpha, b.part_rs, s.n, L.ld, L.nvec, sc, 1, tol, b.prod, prod_sc, (const int32_t*)A->d_perm);
+    GLX_HIP(hipGetLastError());
+    if (ss_blocks) GLX_HIP(hipMemsetAsync(b.ss_stats, 0, 128, st));
+    return reduce<2>(0, ss_blocks);
+  }
+
+  // Dirichlet rows per system (caller row numbers -> record indices)
+  int dirichlet_rows(const int32_t* mask_rows, const int32_t* mask_ptr) {
+    if (s.nmask <= 0) return GLX_OK;
+    const int total = (int)s.nmask;
     std::vector<int32_t> rec(total);
     int most = 0;
-    for (int g = 0; g < ngroups; ++g) most = std::max(most, mask_ptr[g + 1] - mask_ptr[g]);
+    for (int g = 0; g < s.ngroups; ++g) most = std::max(most, mask_ptr[g + 1] - mask_ptr[g]);
     for (int q = 0; q < total; ++q) {
-      GLX_CHECK(mask_rows[q] >= 0 && mask_rows[q] < n, GLX_EINVAL, "glx_cg_groups_masked: row %d out of range", mask_rows[q]);
+      GLX_CHECK(mask_rows[q] >= 0 && mask_rows[q] < s.n, GLX_EINVAL, "glx_cg_groups_masked: row %d out of range", mask_rows[q]);
       rec[q] = A->order_ready && !A->h_inv.empty() ? A->h_inv[mask_rows[q]] : mask_rows[q];
     }
     CG_NEED(b.mask_rows, (size_t)total * 4);
-    CG_NEED(b.mask_ptr, (size_t)(ngroups + 1) * 4);
+    CG_NEED(b.mask_ptr, (size_t)(s.ngroups + 1) * 4);
     GLX_UP(glx_upload_sync(b.mask_rows, rec.data(), (size_t)total * 4, __func__));
-    GLX_UP(glx_upload_sync(b.mask_ptr, mask_ptr, (size_t)(ngroups + 1) * 4, __func__));
-    mask_grid = (unsigned)(((int64_t)most * Cg + 255) / 256);
-    if (ngroups <= 32) {
+    GLX_UP(glx_upload_sync(b.mask_ptr, mask_ptr, (size_t)(s.ngroups + 1) * 4, __func__));
+    mask_grid = (unsigned)(((int64_t)most * s.Cg + 255) / 256);
+    if (s.ngroups <= 32) {
       // the SpMM itself holds A p at zero on these rows (a bit per system in rowmask[record]): no kernel behind it.  (The products
       // p * Ap of such a row are 0 * 0 = +0 instead of 0 * (A p) = +-0: a zero of either sign leaves every running sum as it is.)
-      CG_NEED(b.e_rowmask, (size_t)n * 4);
-      GLX_HIP(hipMemsetAsync(b.e_rowmask, 0, (size_t)n * 4, st));
-      hipLaunchKernelGGL(cg_rowmask_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)ngroups), blk, 0, st, b.e_rowmask,
+      CG_NEED(b.e_rowmask, (size_t)s.n * 4);
+      GLX_HIP(hipMemsetAsync(b.e_rowmask, 0, (size_t)s.n * 4, st));
+      hipLaunchKernelGGL(cg_rowmask_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)s.ngroups), blk, 0, st, b.e_rowmask,
                          (const int32_t*)b.mask_rows, (const int32_t*)b.mask_ptr);
       GLX_HIP(hipGetLastError());
       a.rowmask = b.e_rowmask;
       mask_grid = 0;
     }
+    return GLX_OK;
   }
-  const unsigned pgrid = (unsigned)std::max<int64_t>(((int64_t)n * (L.ld / 4) + 255) / 256, 1);
 
-  std::vector<int64_t> iters(ngroups, 0);       // iterations that ran, per group (utils.py:522 `i`)
-  std::vector<double> err(ngroups, 1.0);        // utils.py:519
-  std::vector<char> done(ngroups, !(1.0 > tol));
-  int running = 0;
-  for (int g = 0; g < ngroups; ++g) running += !done[g];
-  // rows [it0 + 1, it0 + cnt] of the residual history have arrived in `h`: which systems stopped where
-  auto read_history = [&](const double* h, int64_t it0, int64_t cnt) {
-    for (int64_t q = 0; q < cnt && running > 0; ++q) {
-      // iteration it0+q+1 ran for every group whose previous err was > tol; its err decides the next one
-      for (int g = 0; g < ngroups; ++g) {
-        if (done[g]) continue;
-        iters[g] = it0 + q + 1;
-        err[g] = h[(size_t)q * stride + g];
-        if (!(err[g] > tol)) { done[g] = 1; --running; }
-      }
-    }
-  };
   // One iteration of utils.conjgrad's loop (utils.py:521-530) as it is enqueued: `i` = its row in the ring of the residual history
   // (1 .. CG_CHUNK; the kernels test row i - 1 and leave row i), `bl0` / `bl1` = the form of its two reduction chains.
-  auto enqueue_iteration = [&](int i, bool bl0, bool bl1) -> int {
-    a.exit_err = b.err_hist + (size_t)(i - 1) * stride + ngroups;   // all groups converged: exit at once
-    a.act_row = ngroups > 1 ? b.err_hist + (size_t)(i - 1) * stride : nullptr;
-    int rc2 = glx_launch_spmm(a, st);                                               // Ap = A@p, p.Ap partials
-    if (rc2) return rc2;
+  int enqueue_iteration(int i, bool bl0, bool bl1) {
+    a.exit_err = b.err_hist + (size_t)(i - 1) * stride + s.ngroups;   // all groups converged: exit at once
+    a.act_row = s.ngroups > 1 ? b.err_hist + (size_t)(i - 1) * stride : nullptr;
+    GLX_UP(glx_launch_spmm(a, st));                                                 // Ap = A@p, p.Ap partials
     if (mask_grid) {
-      hipLaunchKernelGGL((cg_zero_rows_kernel<T>), dim3(mask_grid, (unsigned)ngroups), blk, 0, st, ap, L.ld, (const int32_t*)b.mask_rows,
-                         (const int32_t*)b.mask_ptr, Cg, sc, i, tol);
+      hipLaunchKernelGGL((cg_zero_rows_kernel<T>), dim3(mask_grid, (unsigned)s.ngroups), blk, 0, st, ap, L.ld, (const int32_t*)b.mask_rows,
+                         (const int32_t*)b.mask_ptr, s.Cg, sc, i, tol);
       GLX_HIP(hipGetLastError());
     }
-    if (np1d) {
-      hipLaunchKernelGGL(cg_pw_leaf_kernel, dim3(pw_grid), dim3(256), 0, st, (const double*)b.prod, prod_sc, pw, sc, i, tol, 0);
-      hipLaunchKernelGGL(cg_pw_tree_kernel<0>, dim3(1), dim3(256), 0, st, pw, sc, i, tol);
-    } else if (bl0) {
-      rc2 = glx_seqsum_run(0, b.prod, n, ncols, C, sc, i, tol, ssw, st);
-      if (rc2) return rc2;
-    } else {
-      hipLaunchKernelGGL(cg_seqsum_dpp_kernel<0>, dim3(seq_grid), dim3(64), 0, st, (const double*)b.prod, n, ncols, C, sc, i, tol);
-    }
-    GLX_HIP(hipGetLastError());
+    GLX_UP(reduce<0>(i, bl0));
     hipLaunchKernelGGL((cg_update_kernel<T, 0>), dim3((unsigned)nb_upd), blk, 0, st, x, r, (const T*)p, (const T*)ap,
-                       (const double*)sc.alpha, b.part_rs, n, L.ld, L.nvec, sc, i, tol, b.prod, prod_sc, (const int32_t*)A->d_perm);
+                       (const double*)sc.alpha, b.part_rs, s.n, L.ld, L.nvec, sc, i, tol, b.prod, prod_sc, (const int32_t*)A->d_perm);
     GLX_HIP(hipGetLastError());
-    if (np1d) {
-      hipLaunchKernelGGL(cg_pw_leaf_kernel, dim3(pw_grid), dim3(256), 0, st, (const double*)b.prod, prod_sc, pw, sc, i, tol, 1);
-      hipLaunchKernelGGL(cg_pw_tree_kernel<1>, dim3(1), dim3(256), 0, st, pw, sc, i, tol);
-    } else if (bl1) {
-      rc2 = glx_seqsum_run(1, b.prod, n, ncols, C, sc, i, tol, ssw, st);
-      if (rc2) return rc2;
-    } else {
-      hipLaunchKernelGGL(cg_seqsum_dpp_kernel<1>, dim3(seq_grid), dim3(64), 0, st, (const double*)b.prod, n, ncols, C, sc, i, tol);
-    }
-    GLX_HIP(hipGetLastError());
-    hipLaunchKernelGGL((cg_pupdate_kernel<T>), dim3(pgrid + 1), blk, 0, st, (const T*)r, p, (const double*)sc.beta, n, L.ld, L.nvec,
+    GLX_UP(reduce<1>(i, bl1));
+    hipLaunchKernelGGL((cg_pupdate_kernel<T>), dim3(pgrid + 1), blk, 0, st, (const T*)r, p, (const double*)sc.beta, s.n, L.ld, L.nvec,
                        sc, i, tol, 2);      // (+ the workgroup of the residual norms: cg_group_err_body)
     GLX_HIP(hipGetLastError());
     return GLX_OK;
-  };
+  }
+
   // a chunk: the ring turns (row 0 <- the last row), then `cnt` iterations
-  auto enqueue_chunk = [&](int cnt, bool bl0, bool bl1) -> int {
+  int enqueue_chunk(int cnt, bool bl0, bool bl1) {
     hipLaunchKernelGGL(cg_roll_hist_kernel, dim3((unsigned)((stride + 255) / 256)), blk, 0, st, b.err_hist, stride, CG_CHUNK);
     GLX_HIP(hipGetLastError());
-    for (int i = 1; i <= cnt; ++i) {
-      int rc2 = enqueue_iteration(i, bl0, bl1);
-      if (rc2) return rc2;
-    }
+    for (int i = 1; i <= cnt; ++i) GLX_UP(enqueue_iteration(i, bl0, bl1));
     return GLX_OK;
-  };
+  }
+
   // Full chunks are replayed from a captured launch sequence (one per combination of reduction forms): the same thirteen-odd launches
   // per iteration, without the host between them.  The sequences belong to the solve parameters they were captured for.
-  const bool use_graphs = !(flags & GLX_CG_EAGER);
-  if (use_graphs) {
-    const std::vector<unsigned long long> key = {
-        (unsigned long long)n, (unsigned long long)C, (unsigned long long)Cg, (unsigned long long)__builtin_bit_cast(unsigned long long, tol),
-        (unsigned long long)dtype, (unsigned long long)flags, (unsigned long long)(uintptr_t)plan, (unsigned long long)(uintptr_t)b.x,
-        (unsigned long long)(uintptr_t)b.r, (unsigned long long)(uintptr_t)b.p, (unsigned long long)(uintptr_t)b.ap,
-        (unsigned long long)(uintptr_t)b.prod, (unsigned long long)(uintptr_t)b.part_dot, (unsigned long long)(uintptr_t)b.part_rs,
-        (unsigned long long)(uintptr_t)b.scal, (unsigned long long)(uintptr_t)b.err_hist, (unsigned long long)(uintptr_t)b.ss_bsum,
-        (unsigned long long)(uintptr_t)b.ss_csum, (unsigned long long)(uintptr_t)b.ss_rec, (unsigned long long)(uintptr_t)b.ss_mask,
-        (unsigned long long)(uintptr_t)b.ss_stats, (unsigned long long)(uintptr_t)b.mask_rows, (unsigned long long)(uintptr_t)b.mask_ptr,
-        (unsigned long long)(uintptr_t)a.rowmask, (unsigned long long)mask_grid, (unsigned long long)(uintptr_t)A->d_perm,
-        (unsigned long long)(uintptr_t)b.pw_vals, (unsigned long long)b.pw_n, (unsigned long long)(uintptr_t)st};
-    if (key != b.e_key) {
-      for (int q = 0; q < 8; ++q)
-        if (b.e_exec[q / 2][q % 2]) { hipGraphExecDestroy(b.e_exec[q / 2][q % 2]); b.e_exec[q / 2][q % 2] = nullptr; }
-      b.e_key = key;
-    }
+  void check_replay_key() {
+    if (!use_graphs) return;
+    const std::vector<unsigned long long> key = cg_replay_key(
+        s.n, s.C, s.Cg, tol, dtype, flags, plan, b.x, b.r, b.p, b.ap, b.prod, b.part_dot, b.part_rs, b.scal, b.err_hist, b.ss_bsum, b.ss_csum,
+        b.ss_rec, b.ss_mask, b.ss_stats, b.mask_rows, b.mask_ptr, a.rowmask, mask_grid, A->d_perm, b.pw_vals, b.pw_n, st);
+    if (key == b.e_key) return;
+    for (int q = 0; q < 8; ++q)
+      if (b.e_exec[q / 2][q % 2]) { hipGraphExecDestroy(b.e_exec[q / 2][q % 2]); b.e_exec[q / 2][q % 2] = nullptr; }
+    b.e_key = key;
   }
-  for (int q = 0; q < 2; ++q)
-    if (!b.e_ev[q]) GLX_HIP(hipEventCreateWithFlags(&b.e_ev[q], hipEventDisableTiming));
+
   // `inst`: the chunk's slot (0 / 1).  Two chunks are in flight at a time and each slot has its OWN instance of the captured sequence:
   // launching an instance that is still running makes the runtime wait for it on the host -- a sleeping wait, ~0.95 ms of idle device per
   // chunk in the first version of this loop (profiles/r06_cg_blocks_kernel_stats.csv has the trace before and after)
-  auto launch_chunk = [&](int cnt, bool bl0, bool bl1, int inst) -> int {
+  int launch_chunk(int cnt, bool bl0, bool bl1, int inst) {
     if (!use_graphs || cnt < CG_CHUNK) return enqueue_chunk(cnt, bl0, bl1);
-    const int v = (bl0 ? 1 : 0) + (bl1 ? 2 : 0);
-    if (!b.e_exec[v][inst]) {
-      hipGraph_t graph = nullptr;
-      GLX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc2 = enqueue_chunk(CG_CHUNK, bl0, bl1);
-      const hipError_t e = hipStreamEndCapture(st, &graph);
-      if (rc2) { if (graph) hipGraphDestroy(graph); return rc2; }
-      GLX_HIP(e);
-      const hipError_t e2 = hipGraphInstantiate(&b.e_exec[v][inst], graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-      GLX_HIP(e2);
-    }
-    GLX_HIP(hipGraphLaunch(b.e_exec[v][inst], st));
+    hipGraphExec_t& exec = b.e_exec[(bl0 ? 1 : 0) + (bl1 ? 2 : 0)][inst];
+    if (!exec) GLX_UP(cg_capture(st, &exec, [&] { return enqueue_chunk(CG_CHUNK, bl0, bl1); }));
+    GLX_HIP(hipGraphLaunch(exec, st));
     return GLX_OK;
-  };
-  {
+  }
+
   // The GPU does not wait for the host: chunk k + 1 is launched before the history of chunk k is looked at (the kernels of iterations
   // past convergence exit at once and leave "stopped" behind them); two chunks in flight, each with its own page-locked slot.
-  struct Flight { int64_t it0; int cnt; int slot; };
-  Flight fl[2];
-  int nfl = 0, slot = 0;
-  int64_t it = 0;                               // iterations launched
-  const size_t slot_doubles = (size_t)(CG_CHUNK + 1) * stride;
-  // A chunk launched ahead runs in the forms decided one look earlier.  While a kind of reduction in block form is anywhere near the price
-  // of the chain (products that cancel: its walk can cost twice the chain), a late switch costs more than the bubble of waiting for the
-  // look: one chunk in flight until the block form has shown itself cheap (under half the chain) or is no longer in use.
-  bool ahead = !(ss_blocks && !blocks_forced);
-  while (running > 0 && (it < max_iter || nfl > 0)) {
-    if (it < max_iter && nfl < (ahead ? 2 : 1)) {
-      const int cnt = (int)std::min<int64_t>(CG_CHUNK, max_iter - it);
-      rc = launch_chunk(cnt, blocks_now[0], blocks_now[1], slot);
-      if (rc) return rc;
-      GLX_HIP(hipMemcpyAsync(b.h_err + slot * slot_doubles, b.err_hist + stride, (size_t)cnt * stride * 8, hipMemcpyDeviceToHost, st));
-      if (ss_blocks) GLX_HIP(hipMemcpyAsync(b.h_ss + slot * 16, b.ss_stats, 128, hipMemcpyDeviceToHost, st));
-      GLX_HIP(hipEventRecord(b.e_ev[slot], st));
-      fl[nfl].it0 = it;
-      fl[nfl].cnt = cnt;
-      fl[nfl].slot = slot;
-      ++nfl;
-      it += cnt;
-      slot ^= 1;
-      if (nfl < (ahead ? 2 : 1) && it < max_iter) continue;
-    }
-    const Flight f = fl[0];
-    fl[0] = fl[1];
-    --nfl;
-    GLX_HIP(hipEventSynchronize(b.e_ev[f.slot]));
-    read_history(b.h_err + f.slot * slot_doubles, f.it0, f.cnt);
-    if (ss_blocks && !blocks_forced) {
-      const unsigned long long* hs = b.h_ss + f.slot * 16;
-      bool cheap = true;
-      for (int m = 0; m < 2; ++m) {
-        if (!blocks_now[m]) continue;
-        const double by_rec = (double)(hs[4 * m + 1] - ss_seen[m][1]), by_rows = (double)(hs[4 * m + 2] - ss_seen[m][2]);
-        for (int q = 0; q < 3; ++q) ss_seen[m][q] = hs[4 * m + q];
-        const double chains = (double)f.cnt * ncols;
-        // measured on one MI355X (profiles/r06_cg_blocks_kernel_stats.csv): 0.7 us per block taken through its record, 1.5 per 256-row
-        // block taken row by row (0.65 of additions -- the chain's 2.4 ns per row --, the rest its rows arriving: three are fetched
-        // ahead per chunk; 399 us for a walk with every one of its 274 blocks row by row), 0.6 per chunk of the walk, 14.5 for the two
-        // passes in front; the chain 2.4 ns per row
-        const double blocks_us = (by_rec * 0.7 + by_rows * 1.5) / chains + ssw.nchunks * 0.6 + 14.5;
-        const double chain_us = (double)n * 0.0024;
-        if (blocks_us > chain_us) blocks_now[m] = false;
-        else if (blocks_us > 0.5 * chain_us) cheap = false;
+  int drive() {
+    struct Flight { int64_t it0; int cnt; int slot; };
+    Flight fl[2];
+    int nfl = 0, slot = 0;
+    int64_t it = 0;                               // iterations launched
+    const size_t slot_doubles = (size_t)(CG_CHUNK + 1) * stride;
+    while (stop.running > 0 && (it < s.max_iter || nfl > 0)) {
+      if (it < s.max_iter && nfl < (forms.ahead ? 2 : 1)) {
+        const int cnt = (int)std::min<int64_t>(CG_CHUNK, s.max_iter - it);
+        GLX_UP(launch_chunk(cnt, forms.blocks_now[0], forms.blocks_now[1], slot));
+        GLX_HIP(hipMemcpyAsync(b.h_err + slot * slot_doubles, b.err_hist + stride, (size_t)cnt * stride * 8, hipMemcpyDeviceToHost, st));
+        if (ss_blocks) GLX_HIP(hipMemcpyAsync(b.h_ss + slot * 16, b.ss_stats, 128, hipMemcpyDeviceToHost, st));
+        GLX_HIP(hipEventRecord(b.e_ev[slot], st));
+        fl[nfl++] = Flight{it, cnt, slot};
+        it += cnt;
+        slot ^= 1;
+        if (nfl < (forms.ahead ? 2 : 1) && it < s.max_iter) continue;
       }
-      ahead = cheap;
+      const Flight f = fl[0];
+      fl[0] = fl[1];
+      --nfl;
+      GLX_HIP(hipEventSynchronize(b.e_ev[f.slot]));
+      stop.read(b.h_err + f.slot * slot_doubles, f.it0, f.cnt);
+      if (ss_blocks) forms.look(b.h_ss + f.slot * 16, f.cnt, s.ncols, s.n, ssw.nchunks);
     }
+    return GLX_OK;
   }
+
+  int finish(void* X, int* iters_out, double* err_out) {
+    if (ss_blocks) GLX_HIP(hipMemcpyAsync(b.h_ss, b.ss_stats, 128, hipMemcpyDeviceToHost, st));
+    GLX_UP(cg_finish(*this, X, rr.out_scale ? b.out_scale : nullptr, iters_out, err_out));
+    for (int q = 0; q < 3; ++q)     // (the entry point hands out ints: clamped, never negative -- -1 is the chain form's mark)
+      b.ss_last[q] = ss_blocks ? (int)std::min<unsigned long long>(b.h_ss[q] + b.h_ss[4 + q] + b.h_ss[8 + q], 0x7fffffffull) : -1;
+    b.ss_last[3] = ss_blocks ? (forms.blocks_now[0] ? 1 : 0) + (forms.blocks_now[1] ? 2 : 0) : -1;
+    return GLX_OK;
   }
-  if (rr.out_scale) {
-    rc = glx_cg_unpack_scaled(dtype, b.x, b.dense, n, L, A->d_perm, b.out_scale, st);
-    if (rc) return rc;
-  } else {
-    rc = glx_unpack_records(b.x, b.dense, n, L, dtype, st, A->d_perm);
-    if (rc) return rc;
-  }
-  GLX_UP(glx_download(X, b.dense, (size_t)n * C * es, st, __func__));
-  if (ss_blocks) GLX_HIP(hipMemcpyAsync(b.h_ss, b.ss_stats, 128, hipMemcpyDeviceToHost, st));
-  GLX_HIP(hipStreamSynchronize(st));
-  for (int q = 0; q < 3; ++q)     // (the entry point hands out ints: clamped, never negative -- -1 is the chain form's mark)
-    b.ss_last[q] = ss_blocks ? (int)std::min<unsigned long long>(b.h_ss[q] + b.h_ss[4 + q] + b.h_ss[8 + q], 0x7fffffffull) : -1;
-  b.ss_last[3] = ss_blocks ? (blocks_now[0] ? 1 : 0) + (blocks_now[1] ? 2 : 0) : -1;
-  for (int g = 0; g < ngroups; ++g) {
-    if (iters_out) iters_out[g] = (int)iters[g];
-    if (err_out) err_out[g] = err[g];
-  }
-  return GLX_OK;
+};
+
+template <typename T>
+static int cg_run(glx_graph* A, const void* B, void* X, int C, int Cg, double tol, int64_t max_iter, int* iters_out,
+                  double* err_out, int flags, const int32_t* mask_rows, const int32_t* mask_ptr, const CgRhsRows& rr) {
+  if (flags & GLX_CG_TREE)     // tolerance mode: cg_fused.hip (deterministic, not bit-identical to numpy's chains)
+    return glx_cg_run_fused(A, B, X, C, Cg, tol, max_iter, iters_out, err_out, flags, mask_rows, mask_ptr, rr);
+  CgExact<T> c(A, C, Cg, tol, max_iter, flags, rr);
+  GLX_UP(c.open(mask_rows, mask_ptr));
+  GLX_UP(c.block_form_ready());
+  GLX_UP(c.pairwise_plan_ready());
+  GLX_UP(c.load_problem(B, X));
+  GLX_UP(c.dirichlet_rows(mask_rows, mask_ptr));
+  c.check_replay_key();
+  GLX_UP(c.drive());
+  return c.finish(X, iters_out, err_out);
 }
 
 static int cg_entry(glx_graph* A, const void* B, void* X, int C, int group_cols, const int32_t* mask_rows, const int32_t* mask_ptr,

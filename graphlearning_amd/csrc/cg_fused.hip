@@ -266,281 +266,179 @@ int glx_cg_unpack_scaled(int dtype, const void* rec, void* dense, int64_t n, con
 }
 
 // ---- the solve ---------------------------------------------------------------------------------------------------------------
-// Iterations per captured chunk.  Every hand-over from one launched graph to the next costs ~37 us of idle device (kernel trace:
-// profiles/r04_cg_tree_chunks.txt) whether or not the next one was enqueued in time, an iteration past convergence ~9 us (its two
-// kernels exit at once): long chunks while the end is far, short ones near it.
-static const int CG_NLEN = 3;
-static const int CG_LEN[CG_NLEN] = {32, 16, 4};
-static const int CG_LONG = 32;                 // (the longest: sizes the history buffers)
+struct CgFused : CgSolve {
+  using CgSolve::CgSolve;
+  int rpb = 0, nb2 = 1, grp = 32;
+  int64_t ngrp = 1, hist_cap = 0;
+  CgStage stage;                  // offsets of the one staged upload
+  CgDev cd;
+  bool keep_x = false;            // X holds x0 on entry; B is the caller's r0 = b - A@x0 (utils.py:510-514)
 
-int glx_cg_run_fused(glx_graph* A, const void* B, void* X, int C, int Cg, double tol, int64_t max_iter, int* iters_out, double* err_out,
-                     int flags, const int32_t* mask_rows, const int32_t* mask_ptr, const CgRhsRows& rr) {
-  const int ngroups = C / Cg;
-  const int stride = ngroups + 1;
-  const int64_t n = A->n_rows;
-  const int dtype = A->dtype;
-  RecLayout L;
-  int rc = glx_make_layout(C, dtype, false, &L);
-  if (rc) return rc;
-  SellPlan* plan = nullptr;
-  rc = glx_graph_plan(A, L.G, &plan, true);      // the relaxed image: a row's segments sum independently (graph.hip)
-  if (rc) return rc;
-  const size_t es = L.esize;
-  const int ncols = L.nvec * 4;
-  GLX_CHECK(ncols <= 256, GLX_EUNSUPPORTED, "glx_cg_multi: C=%d too wide for the column reducer", C);
-  GLX_CHECK(256 / (L.ld / 4) >= 1, GLX_EUNSUPPORTED, "glx_cg_multi: record too wide");
-  GLX_CHECK(max_iter < (1ll << 24), GLX_EUNSUPPORTED, "glx_cg_multi: max_iter %lld exceeds the supported 2^24-1", (long long)max_iter);
-  const int64_t nmask = (mask_rows && mask_ptr) ? mask_ptr[ngroups] : 0;
-  GLX_CHECK(nmask == 0 || ngroups <= 32, GLX_EUNSUPPORTED,
-            "glx_cg_groups_masked: at most 32 systems with Dirichlet rows per tolerance-mode solve (got %d)", ngroups);
-  for (int64_t q = 0; q < nmask; ++q)
-    GLX_CHECK(mask_rows[q] >= 0 && mask_rows[q] < n, GLX_EINVAL, "glx_cg_groups_masked: row %d out of range", mask_rows[q]);
-  const int64_t nb_spmm = std::max<int64_t>(glx_spmm_blocks(plan), 1);
-  int rpb = 0;
-  const int nb2 = glx_cg_fused_update_blocks(n, &rpb);
-  // groups of SpMM workgroups: small enough that a group's last arriver adds its rows in one round of loads, few enough that
-  // every workgroup of the update kernel can add the groups for itself
-  const int grp = (int)std::max<int64_t>(32, (nb_spmm + 63) / 64);
-  const int64_t ngrp = (nb_spmm + grp - 1) / grp;
-  const int nq = 3 * ncols;
-  const int64_t hist_cap = max_iter + 2 + 2 * CG_LONG;   // whole chunks of rows are copied, one chunk ahead
+  int open(const int32_t* mask_rows, const int32_t* mask_ptr) {
+    GLX_UP(cg_open(*this, true, cg_fused_limits, mask_rows, mask_ptr));      // the relaxed image: a row's segments sum independently (graph.hip)
+    for (int64_t q = 0; q < s.nmask; ++q)
+      GLX_CHECK(mask_rows[q] >= 0 && mask_rows[q] < s.n, GLX_EINVAL, "glx_cg_groups_masked: row %d out of range", mask_rows[q]);
+    keep_x = (flags & GLX_CG_X0) != 0;
+    nb2 = glx_cg_fused_update_blocks(s.n, &rpb);
+    // groups of SpMM workgroups: small enough that a group's last arriver adds its rows in one round of loads, few enough that
+    // every workgroup of the update kernel can add the groups for itself
+    grp = (int)std::max<int64_t>(32, (nb_spmm + 63) / 64);
+    ngrp = (nb_spmm + grp - 1) / grp;
+    const int nq = 3 * s.ncols;
+    hist_cap = s.max_iter + 2 + 2 * CG_LONG;   // whole chunks of rows are copied, one chunk ahead
+    if (!b.side) GLX_HIP(hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking));
+    for (int q = 0; q < 3; ++q)
+      if (!b.f_ev[q]) GLX_HIP(hipEventCreateWithFlags(&b.f_ev[q], hipEventDisableTiming));
+    CG_NEED(b.err_hist, (size_t)hist_cap * stride * 8);
+    CG_NEED(b.f_part1, (size_t)nb_spmm * nq * 8);
+    CG_NEED(b.f_part1g, (size_t)ngrp * nq * 8);
+    CG_NEED(b.f_part2, (size_t)nb2 * s.ncols * 8);
+    CG_NEED(b.f_tick, (size_t)(ngrp + 1) * 4);
+    CG_NEED(b.f_it, 64);
+    if (s.nmask) CG_NEED(b.f_rowmask, (size_t)s.n * 4);
+    return GLX_OK;
+  }
 
-  if (!A->cg_ws) A->cg_ws = new CgBufs();
-  CgBufs& b = *(CgBufs*)A->cg_ws;
-  const size_t recb = std::max<size_t>((size_t)n * L.ld * es, 64);
-  if (!b.stream) GLX_HIP(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
-  if (!b.side) GLX_HIP(hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking));
-  for (int q = 0; q < 3; ++q)
-    if (!b.f_ev[q]) GLX_HIP(hipEventCreateWithFlags(&b.f_ev[q], hipEventDisableTiming));
-  hipStream_t st = b.stream;
-  CG_NEED(b.x, recb);
-  CG_NEED(b.r, recb);
-  CG_NEED(b.p, recb);
-  CG_NEED(b.ap, recb);
-  CG_NEED(b.dense, (size_t)n * C * es);
-  CG_NEED(b.scal, (size_t)3 * ncols * 8);
-  CG_NEED(b.err_hist, (size_t)hist_cap * stride * 8);
-  CG_NEED(b.f_part1, (size_t)nb_spmm * nq * 8);
-  CG_NEED(b.f_part1g, (size_t)ngrp * nq * 8);
-  CG_NEED(b.f_part2, (size_t)nb2 * ncols * 8);
-  CG_NEED(b.f_tick, (size_t)(ngrp + 1) * 4);
-  CG_NEED(b.f_it, 64);
-  if (nmask) CG_NEED(b.f_rowmask, (size_t)n * 4);
-  {
-    // the host's mirror of the residual history: the maximum slot of every row a solve may write holds NaN = "not yet written"
-    // A marker is only where the LAYOUT of the solve that armed it put it: another number of systems (ssl_trials' stacked solve
-    // followed by a single fit on the same operator) or a longer history moves the marker slots onto words that hold an earlier
-    // solve's residuals, which the poll below would take for rows already written.  So the markers are re-armed row by row only
-    // while the layout stays the same; any change (or a new buffer) fills the whole mirror.
+  // the host's mirror of the residual history: the maximum slot of every row a solve may write holds NaN = "not yet written"
+  // A marker is only where the LAYOUT of the solve that armed it put it: another number of systems (ssl_trials' stacked solve
+  // followed by a single fit on the same operator) or a longer history moves the marker slots onto words that hold an earlier
+  // solve's residuals, which the poll below would take for rows already written.  So the markers are re-armed row by row only
+  // while the layout stays the same; any change (or a new buffer) fills the whole mirror.
+  int arm_history_mirror() {
     const bool fresh = !b.h_hist || b.h_hist_rows < hist_cap * stride || b.h_hist_stride != stride;
-    int rc_ = b.need_host(&b.h_hist, (size_t)hist_cap * stride * 8);
-    if (rc_) return rc_;
+    CG_NEED_HOST(b.h_hist, (size_t)hist_cap * stride * 8);
     const double not_yet = std::numeric_limits<double>::quiet_NaN();
     if (fresh) {
-      const int64_t words = (int64_t)(b.cap[(void**)&b.h_hist] / 8);
+      const int64_t words = (int64_t)(b.cap[(void**)&b.h_hist].bytes / 8);
       for (int64_t j = 0; j < words; ++j) b.h_hist[j] = not_yet;
       b.h_hist_rows = words;
       b.h_hist_stride = stride;
     } else {
-      for (int64_t j = 0; j <= std::min<int64_t>(b.h_hist_dirty, hist_cap - 1); ++j) b.h_hist[(size_t)j * stride + ngroups] = not_yet;
+      for (int64_t j = 0; j <= std::min<int64_t>(b.h_hist_dirty, hist_cap - 1); ++j) b.h_hist[(size_t)j * stride + s.ngroups] = not_yet;
     }
     b.h_hist_dirty = 0;
+    return GLX_OK;
   }
 
   // one upload: [right-hand side rows | Dirichlet rows | their systems | values | output scale]
-  const size_t o_rows = 0, o_mrows = o_rows + (size_t)rr.nb * 4, o_mgrp = o_mrows + (size_t)nmask * 4;
-  const size_t o_vals = (o_mgrp + (size_t)nmask * 4 + 15) / 16 * 16;
-  const size_t o_scale = (o_vals + (rr.rows ? (size_t)rr.nb * C * es : 0) + 15) / 16 * 16;
-  const size_t stage_bytes = o_scale + (rr.out_scale ? (size_t)n * 8 : 0);
-  if (stage_bytes) {
-    CG_NEED(b.f_stage, stage_bytes);
-    { int rc_ = b.need_host(&b.h_stage, stage_bytes); if (rc_) return rc_; }
+  int stage_rows(const int32_t* mask_rows, const int32_t* mask_ptr) {
+    stage = cg_stage_layout(rr.nb, s.nmask, s.C, L.esize, rr.out_scale ? s.n : 0);
+    if (!stage.bytes) return GLX_OK;
+    CG_NEED(b.f_stage, stage.bytes);
+    CG_NEED_HOST(b.h_stage, stage.bytes);
     if (rr.rows && rr.nb) {
-      memcpy(b.h_stage + o_rows, rr.rows, (size_t)rr.nb * 4);
-      memcpy(b.h_stage + o_vals, rr.vals, (size_t)rr.nb * C * es);
+      memcpy(b.h_stage + stage.rows, rr.rows, (size_t)rr.nb * 4);
+      memcpy(b.h_stage + stage.vals, rr.vals, (size_t)rr.nb * s.C * L.esize);
     }
-    for (int g = 0; g < ngroups && nmask; ++g)
+    for (int g = 0; g < s.ngroups && s.nmask; ++g)
       for (int q = mask_ptr[g]; q < mask_ptr[g + 1]; ++q) {
-        ((int32_t*)(b.h_stage + o_mrows))[q] = mask_rows[q];
-        ((int32_t*)(b.h_stage + o_mgrp))[q] = g;
+        ((int32_t*)(b.h_stage + stage.mrows))[q] = mask_rows[q];
+        ((int32_t*)(b.h_stage + stage.mgrp))[q] = g;
       }
-    if (rr.out_scale) memcpy(b.h_stage + o_scale, rr.out_scale, (size_t)n * 8);
-    GLX_HIP(hipMemcpyAsync(b.f_stage, b.h_stage, stage_bytes, hipMemcpyHostToDevice, st));
+    if (rr.out_scale) memcpy(b.h_stage + stage.scale, rr.out_scale, (size_t)s.n * 8);
+    GLX_HIP(hipMemcpyAsync(b.f_stage, b.h_stage, stage.bytes, hipMemcpyHostToDevice, st));
+    return GLX_OK;
   }
-  const bool keep_x = (flags & GLX_CG_X0) != 0;
-  if (keep_x) {   // X holds x0 on entry; B is the caller's r0 = b - A@x0 (utils.py:510-514)
-    GLX_UP(glx_upload(b.dense, X, (size_t)n * C * es, st, __func__));
-    rc = glx_pack_records(b.dense, b.x, n, L, dtype, nullptr, st, A->d_perm);
-    if (rc) return rc;
-  }
-  if (rr.rows) {
+
+  // x0, and r = b where it is dense (r = b - A@0 = b, utils.py:514); given by rows, r is zeroed for scatter_rows
+  int load_problem(const void* B, const void* X) {
+    if (keep_x) GLX_UP(cg_load_dense(*this, X, b.x));
+    if (!rr.rows) return cg_load_dense(*this, B, b.r);
     GLX_HIP(hipMemsetAsync(b.r, 0, recb, st));
-  } else {
-    GLX_UP(glx_upload(b.dense, B, (size_t)n * C * es, st, __func__));
-    rc = glx_pack_records(b.dense, b.r, n, L, dtype, nullptr, st, A->d_perm);   // r = b - A@0 = b (utils.py:514)
-    if (rc) return rc;
+    return GLX_OK;
   }
-  if (nmask) GLX_HIP(hipMemsetAsync(b.f_rowmask, 0, (size_t)n * 4, st));
-  if ((rr.rows && rr.nb) || nmask) {
-    const int64_t work = std::max<int64_t>(rr.rows ? rr.nb * C : 0, nmask);
-    const dim3 grid((unsigned)((work + 255) / 256));
-    if (dtype == GLX_F32)
-      hipLaunchKernelGGL(cg_fused_scatter_kernel<float>, grid, dim3(256), 0, st, (float*)b.r, L.ld, C, (const int32_t*)(b.f_stage + o_rows),
-                         (const float*)(b.f_stage + o_vals), rr.rows ? rr.nb : 0, (const int32_t*)A->d_inv, b.f_rowmask,
-                         (const int32_t*)(b.f_stage + o_mrows), (const int32_t*)(b.f_stage + o_mgrp), nmask);
-    else
-      hipLaunchKernelGGL(cg_fused_scatter_kernel<double>, grid, dim3(256), 0, st, (double*)b.r, L.ld, C, (const int32_t*)(b.f_stage + o_rows),
-                         (const double*)(b.f_stage + o_vals), rr.rows ? rr.nb : 0, (const int32_t*)A->d_inv, b.f_rowmask,
-                         (const int32_t*)(b.f_stage + o_mrows), (const int32_t*)(b.f_stage + o_mgrp), nmask);
+
+  // the staged right-hand side rows into r, the staged Dirichlet rows as bits of rowmask
+  template <typename T> int scatter_rows() {
+    if (s.nmask) GLX_HIP(hipMemsetAsync(b.f_rowmask, 0, (size_t)s.n * 4, st));
+    if (!((rr.rows && rr.nb) || s.nmask)) return GLX_OK;
+    const int64_t work = std::max<int64_t>(rr.rows ? rr.nb * s.C : 0, s.nmask);
+    hipLaunchKernelGGL(cg_fused_scatter_kernel<T>, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, (T*)b.r, L.ld, s.C,
+                       (const int32_t*)(b.f_stage + stage.rows), (const T*)(b.f_stage + stage.vals), rr.rows ? rr.nb : 0,
+                       (const int32_t*)A->d_inv, b.f_rowmask, (const int32_t*)(b.f_stage + stage.mrows),
+                       (const int32_t*)(b.f_stage + stage.mgrp), s.nmask);
     GLX_HIP(hipGetLastError());
+    return GLX_OK;
   }
-  CgDev cd;
-  memset(&cd, 0, sizeof(cd));
-  cd.rsold = b.scal;
-  cd.err_hist = b.err_hist;
-  cd.stride = stride;
-  cd.ngroups = ngroups;
-  cd.Cg = Cg;
-  cd.C = C;
-  cd.max_iter = (int)max_iter;
-  cd.it_a = b.f_it;
-  cd.it_b = b.f_it + 4;
-  cd.closed = b.f_it + 8;
-  cd.r = (const char*)b.r;
-  cd.part1 = b.f_part1;
-  cd.part1g = b.f_part1g;
-  cd.tick1 = b.f_tick;
-  cd.grp = grp;
-  cd.ngrp = (int)ngrp;
-  cd.part2 = b.f_part2;
-  cd.nb2 = nb2;
-  {
+
+  // what the kernels of the solve are given (CgDev), and x = 0 | x0, p = r, the partial sums of r.r, the counters
+  template <typename T> int init_iterates() {
+    memset(&cd, 0, sizeof(cd));
+    cd.rsold = b.scal;
+    cd.err_hist = b.err_hist;
+    cd.stride = stride;
+    cd.ngroups = s.ngroups;
+    cd.Cg = s.Cg;
+    cd.C = s.C;
+    cd.max_iter = (int)s.max_iter;
+    cd.it_a = b.f_it;
+    cd.it_b = b.f_it + 4;
+    cd.closed = b.f_it + 8;
+    cd.r = (const char*)b.r;
+    cd.part1 = b.f_part1;
+    cd.part1g = b.f_part1g;
+    cd.tick1 = b.f_tick;
+    cd.grp = grp;
+    cd.ngrp = (int)ngrp;
+    cd.part2 = b.f_part2;
+    cd.nb2 = nb2;
     void* view = nullptr;
     GLX_HIP(hipHostGetDevicePointer(&view, b.h_hist, 0));
     cd.host_hist = (double*)view;
+    hipLaunchKernelGGL(cg_fused_init_kernel<T>, dim3((unsigned)nb2), dim3(256), 0, st, (T*)b.x, (const T*)b.r, (T*)b.p, s.n, L.ld, L.nvec, cd,
+                       rpb, keep_x ? 1 : 0);
+    GLX_HIP(hipGetLastError());
+    a.rowmask = s.nmask ? b.f_rowmask : nullptr;
+    a.cg = &cd;
+    return GLX_OK;
   }
-  if (dtype == GLX_F32)
-    hipLaunchKernelGGL(cg_fused_init_kernel<float>, dim3((unsigned)nb2), dim3(256), 0, st, (float*)b.x, (const float*)b.r, (float*)b.p, n, L.ld,
-                       L.nvec, cd, rpb, keep_x ? 1 : 0);
-  else
-    hipLaunchKernelGGL(cg_fused_init_kernel<double>, dim3((unsigned)nb2), dim3(256), 0, st, (double*)b.x, (const double*)b.r, (double*)b.p, n,
-                       L.ld, L.nvec, cd, rpb, keep_x ? 1 : 0);
-  GLX_HIP(hipGetLastError());
 
-  SweepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.plan = plan;
-  a.L = L;
-  a.dtype = dtype;
-  a.xin = b.p;
-  a.xout = b.ap;
-  a.n_rows = n;
-  a.exit_tol = tol;
-  a.act_cg = Cg;
-  a.act_c = C;
-  a.rowmask = nmask ? b.f_rowmask : nullptr;
-  a.cg = &cd;
-  auto enqueue_chunk = [&](int iters) -> int {
+  int enqueue_chunk(int iters) {
     for (int q = 0; q < iters; ++q) {
-      int rc2 = glx_launch_spmm(a, st);                                                      // Ap = A@p, dots; closes the previous iteration
-      if (rc2) return rc2;
-      rc2 = glx_cg_fused_update(dtype, b.x, b.r, b.p, b.ap, n, L, cd, tol, st);              // alpha, beta, x, r, p, r.r
-      if (rc2) return rc2;
+      GLX_UP(glx_launch_spmm(a, st));                                                          // Ap = A@p, dots; closes the previous iteration
+      GLX_UP(glx_cg_fused_update(dtype, b.x, b.r, b.p, b.ap, s.n, L, cd, tol, st));            // alpha, beta, x, r, p, r.r
     }
-    return glx_cg_fused_close(cd, tol, st);                                                  // the chunk's last err
-  };
-  // everything the captured kernels were given: a replay is only valid for the same arguments
-  std::vector<unsigned long long> key = {(unsigned long long)(uintptr_t)plan, (unsigned long long)(uintptr_t)plan->d_col,
-                                         (unsigned long long)(uintptr_t)b.x, (unsigned long long)(uintptr_t)b.r,
-                                         (unsigned long long)(uintptr_t)b.p, (unsigned long long)(uintptr_t)b.ap,
-                                         (unsigned long long)(uintptr_t)b.scal, (unsigned long long)(uintptr_t)b.err_hist,
-                                         (unsigned long long)(uintptr_t)b.f_part1, (unsigned long long)(uintptr_t)b.f_part1g,
-                                         (unsigned long long)grp, (unsigned long long)(uintptr_t)b.f_part2,
-                                         (unsigned long long)(uintptr_t)b.f_tick, (unsigned long long)(uintptr_t)b.f_it,
-                                         (unsigned long long)(uintptr_t)a.rowmask, (unsigned long long)(uintptr_t)cd.host_hist, (unsigned long long)C, (unsigned long long)Cg,
-                                         (unsigned long long)max_iter, (unsigned long long)n, (unsigned long long)dtype, 0ull};
-  memcpy(&key.back(), &tol, 8);
-  if (!b.f_exec[0] || b.f_key != key) {
+    return glx_cg_fused_close(cd, tol, st);                                                    // the chunk's last err
+  }
+
+  // the three chunk lengths as captured launch sequences, kept while everything the captured kernels were given stays the same
+  int capture_chunks() {
+    const std::vector<unsigned long long> key =
+        cg_replay_key(plan, plan->d_col, b.x, b.r, b.p, b.ap, b.scal, b.err_hist, b.f_part1, b.f_part1g, grp, b.f_part2, b.f_tick, b.f_it,
+                      a.rowmask, cd.host_hist, s.C, s.Cg, s.max_iter, s.n, dtype, tol);
+    if (b.f_exec[0] && b.f_key == key) return GLX_OK;
     for (int v = 0; v < CG_NLEN; ++v) {
       if (b.f_exec[v]) { hipGraphExecDestroy(b.f_exec[v]); b.f_exec[v] = nullptr; }
-      hipGraph_t graph;
-      GLX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      rc = enqueue_chunk(CG_LEN[v]);
-      hipError_t e = hipStreamEndCapture(st, &graph);
-      if (rc) return rc;
-      GLX_HIP(e);
-      GLX_HIP(hipGraphInstantiate(&b.f_exec[v], graph, nullptr, nullptr, 0));
-      GLX_HIP(hipGraphDestroy(graph));
+      GLX_UP(cg_capture(st, &b.f_exec[v], [&] { return enqueue_chunk(CG_LEN[v]); }));
     }
     b.f_key = key;
+    return GLX_OK;
   }
 
-  std::vector<int64_t> iters(ngroups, 0);       // iterations that ran, per system (utils.py:522 `i`)
-  std::vector<double> err(ngroups, 1.0);        // utils.py:519
-  std::vector<char> done(ngroups, !(1.0 > tol));
-  int running = 0;
-  for (int g = 0; g < ngroups; ++g) running += !done[g];
-  double e_prev = 1.0, e_last = 1.0;            // the two latest maxima over the running systems the host has seen
-  double margin_seen = INFINITY;                // min over every decision taken of |err - tol| / tol (glx_cg_last_stop_margin)
-  auto read_history = [&](const double* h, int64_t it0, int64_t cnt) {
-    for (int64_t q = 0; q < cnt && running > 0; ++q) {
-      // iteration it0+q+1 ran for every system whose previous err was > tol; its err decides the next one
-      for (int g = 0; g < ngroups; ++g) {
-        if (done[g]) continue;
-        iters[g] = it0 + q + 1;
-        err[g] = h[(size_t)q * stride + g];
-        // EVERY residual norm a running system shows is a stop decision (CG's residual norms are not monotone: one that came within
-        // the band of tol on the far side iterations ago could have stopped the reference's order of additions there)
-        if (tol > 0 && err[g] == err[g]) margin_seen = std::min(margin_seen, fabs(err[g] - tol) / tol);
-        if (!(err[g] > tol)) { done[g] = 1; --running; }
-      }
-      e_prev = e_last;
-      e_last = h[(size_t)q * stride + ngroups];
-    }
-  };
   // The GPU never waits for the host: the next chunk is launched before the history of the previous one is looked at (kernels of
   // iterations past convergence exit at once).  The first chunk has 16 iterations and the one launched blind behind it 4; from then
-  // on the residuals the host has seen choose -- CG's error falls roughly geometrically, the last ratio predicts the iterations still
-  // needed, and the longest chunk that does not overshoot them by more than two is launched.
-  struct Flight { int slot; int64_t it0; int cnt; };
-  Flight fl[2];
-  int nfl = 0, slot = 0;
-  int64_t launched = 0, looked = 0;
-  auto launch_chunk = [&](int v) -> int {
-    const int len = CG_LEN[v];
-    GLX_HIP(hipGraphLaunch(b.f_exec[v], st));
-    // (nothing else goes into the stream between two chunks: the closing kernels write the history into the host's page-locked
-    // mirror themselves -- an event record + copy here cost a ~37 us bubble per chunk, profiles/r04_cg_tree_chunks.txt)
-    fl[nfl].slot = slot;
-    fl[nfl].it0 = launched;
-    fl[nfl].cnt = len;
-    ++nfl;
-    launched += len;
-    slot ^= 1;
-    return GLX_OK;
-  };
-  auto next_kind = [&]() -> int {
-    if (looked < 4) return CG_NLEN - 1;                           // nothing seen yet: the short chunk behind the first one
-    if (!(e_last > tol) || !(e_last < e_prev)) return 1;
-    const double rate = e_last / e_prev;
-    const double need = log(tol / e_last) / log(rate);           // iterations still needed after `looked`
-    const double open = need - (double)(launched - looked);      // ... of which not yet launched
-    for (int v = 0; v < CG_NLEN - 1; ++v)
-      if ((double)CG_LEN[v] <= open + 2.0) return v;
-    return CG_NLEN - 1;
-  };
-  if (running > 0 && max_iter > 0) {
-    rc = launch_chunk(1);
-    if (rc) return rc;
-    while (running > 0 && looked < max_iter) {
-      if (launched < max_iter && nfl < 2) {
-        rc = launch_chunk(next_kind());
-        if (rc) return rc;
-      }
-      const int64_t cnt = std::min<int64_t>(fl[0].cnt, max_iter - fl[0].it0);
-      for (int64_t q = 0; q < cnt && running > 0; ++q) {
+  // on the residuals the host has seen choose (cg_next_kind).
+  int drive() {
+    struct Flight { int64_t it0; int cnt; };
+    Flight fl[2];
+    int nfl = 0;
+    int64_t launched = 0, looked = 0;
+    auto launch_chunk = [&](int v) -> int {
+      GLX_HIP(hipGraphLaunch(b.f_exec[v], st));
+      // (nothing else goes into the stream between two chunks: the closing kernels write the history into the host's page-locked
+      // mirror themselves -- an event record + copy here cost a ~37 us bubble per chunk, profiles/r04_cg_tree_chunks.txt)
+      fl[nfl++] = Flight{launched, CG_LEN[v]};
+      launched += CG_LEN[v];
+      return GLX_OK;
+    };
+    if (!(stop.running > 0 && s.max_iter > 0)) return GLX_OK;
+    GLX_UP(launch_chunk(1));
+    while (stop.running > 0 && looked < s.max_iter) {
+      if (launched < s.max_iter && nfl < 2) GLX_UP(launch_chunk(cg_next_kind(looked, launched, stop.e_prev, stop.e_last, tol)));
+      const int64_t cnt = std::min<int64_t>(fl[0].cnt, s.max_iter - fl[0].it0);
+      for (int64_t q = 0; q < cnt && stop.running > 0; ++q) {
         // row it0+q+1 is written by the kernels of the chunk in flight: iteration it0+q+1 runs because the row before said so
-        const volatile double* slot_max = b.h_hist + (size_t)(fl[0].it0 + q + 1) * stride + ngroups;
+        const volatile double* slot_max = b.h_hist + (size_t)(fl[0].it0 + q + 1) * stride + s.ngroups;
         int spins = 0;
         bool idle_seen = false;
         while (*slot_max != *slot_max) {
@@ -556,32 +454,36 @@ int glx_cg_run_fused(glx_graph* A, const void* B, void* X, int C, int Cg, double
           }
         }
         std::atomic_thread_fence(std::memory_order_acquire);
-        read_history((const double*)b.h_hist + (size_t)(fl[0].it0 + q + 1) * stride, fl[0].it0 + q, 1);
+        stop.read((const double*)b.h_hist + (size_t)(fl[0].it0 + q + 1) * stride, fl[0].it0 + q, 1);
       }
       looked = fl[0].it0 + fl[0].cnt;
       fl[0] = fl[1];
       --nfl;
     }
     b.h_hist_dirty = launched + 1;
+    return GLX_OK;
   }
-  if (rr.out_scale) {
-    rc = glx_cg_unpack_scaled(dtype, b.x, b.dense, n, L, A->d_perm, (const double*)(b.f_stage + o_scale), st);
-  } else {
-    rc = glx_unpack_records(b.x, b.dense, n, L, dtype, st, A->d_perm);
-  }
-  if (rc) return rc;
-  GLX_UP(glx_download(X, b.dense, (size_t)n * C * es, st, __func__));
-  GLX_HIP(hipStreamSynchronize(st));
+};
+
+int glx_cg_run_fused(glx_graph* A, const void* B, void* X, int C, int Cg, double tol, int64_t max_iter, int* iters_out, double* err_out,
+                     int flags, const int32_t* mask_rows, const int32_t* mask_ptr, const CgRhsRows& rr) {
+  CgFused c(A, C, Cg, tol, max_iter, flags, rr);
+  const bool f32 = A->dtype == GLX_F32;
+  GLX_UP(c.open(mask_rows, mask_ptr));
+  GLX_UP(c.arm_history_mirror());
+  GLX_UP(c.stage_rows(mask_rows, mask_ptr));
+  GLX_UP(c.load_problem(B, X));
+  GLX_UP(f32 ? c.scatter_rows<float>() : c.scatter_rows<double>());
+  GLX_UP(f32 ? c.init_iterates<float>() : c.init_iterates<double>());
+  GLX_UP(c.capture_chunks());
+  GLX_UP(c.drive());
+  GLX_UP(cg_finish(c, X, rr.out_scale ? (const double*)(c.b.f_stage + c.stage.scale) : nullptr, iters_out, err_out));
   // How close the stop decisions of this solve came to going the other way (glx_cg_last_stop_margin): the smallest relative distance
   // from `tol` of ANY residual norm a running system showed -- the one that passed the test, the last one that failed it, and every
   // earlier one (residual norms of CG are not monotone).  The reordered reductions of this mode move a residual norm by a relative
   // 1e-13 .. 1e-8 (more after hundreds of iterations); a decision with a margin below that could have gone the other way with the
   // reference's order of additions.
-  b.last_stop_margin = margin_seen;
-  for (int g = 0; g < ngroups; ++g) {
-    if (iters_out) iters_out[g] = (int)iters[g];
-    if (err_out) err_out[g] = err[g];
-  }
+  c.b.last_stop_margin = c.stop.margin_seen;
   return GLX_OK;
 }
 

@@ -1,9 +1,8 @@
 // Shared by cg.hip (reference-order conjugate gradient) and cg_fused.hip (tolerance mode).
 #pragma once
 #include "glx_internal.h"
+#include "cg_plan.h"
 #include <map>
-#include <vector>
-#include <algorithm>
 
 struct PwPlan {          // device arrays; value index space: leaves [0, nleaves), internal nodes after them by height
   const int64_t* leaf_off;
@@ -54,7 +53,8 @@ struct CgBufs {
   std::vector<unsigned long long> f_key;
   hipEvent_t f_ev[3] = {nullptr, nullptr, nullptr};
   hipStream_t stream = nullptr, side = nullptr;
-  std::map<void**, size_t> cap;
+  struct Block { size_t bytes; bool host; };
+  std::map<void**, Block> cap;     // every block need() / need_host() handed out: what the destructor frees
   int64_t pw_n = -1;   // rows the pairwise-summation plan was built for
   PwPlan pw;
   unsigned pw_grid = 1;
@@ -62,42 +62,35 @@ struct CgBufs {
   int need(void** ptr, size_t bytes) {
     bytes = std::max<size_t>(bytes, 64);
     auto it = cap.find(ptr);
-    if (it != cap.end() && it->second >= bytes && *ptr) return GLX_OK;
+    if (it != cap.end() && it->second.bytes >= bytes && *ptr) return GLX_OK;
     hipFree(*ptr);
     *ptr = nullptr;
-    cap[ptr] = 0;
+    cap[ptr] = {0, false};
     GLX_HIP(hipMalloc(ptr, bytes));
-    cap[ptr] = bytes;
+    cap[ptr].bytes = bytes;
     return GLX_OK;
   }
-  template <class P> int need_host(P** ptr, size_t bytes) {
+  template <class P> int need_host(P** ptr, size_t bytes) {   // the same, page-locked
     auto it = cap.find((void**)ptr);
-    if (it != cap.end() && it->second >= bytes && *ptr) return GLX_OK;
+    if (it != cap.end() && it->second.bytes >= bytes && *ptr) return GLX_OK;
     if (*ptr) hipHostFree(*ptr);
     *ptr = nullptr;
-    cap[(void**)ptr] = 0;
+    cap[(void**)ptr] = {0, true};
     GLX_HIP(hipHostMalloc((void**)ptr, bytes, hipHostMallocDefault));
-    cap[(void**)ptr] = bytes;
+    cap[(void**)ptr].bytes = bytes;
     return GLX_OK;
   }
-  ~CgBufs() {
-    hipFree(x); hipFree(r); hipFree(p); hipFree(ap); hipFree(dense); hipFree(part_dot); hipFree(part_rs);
-    hipFree(scal); hipFree(err_hist); hipFree(prod);
-    hipFree(pw_off); hipFree(pw_len); hipFree(pw_l); hipFree(pw_r); hipFree(pw_ls); hipFree(pw_vals); hipFree(mask_rows); hipFree(mask_ptr);
-    hipFree(rhs_rows); hipFree(out_scale);
-    hipFree(f_part1); hipFree(f_part1g); hipFree(f_part2); hipFree(f_tick); hipFree(f_rowmask); hipFree(f_it);
-    hipFree(f_stage);
-    hipFree(ss_bsum); hipFree(ss_csum); hipFree(ss_rec); hipFree(ss_mask); hipFree(ss_stats); hipFree(e_rowmask);
+  ~CgBufs() {   // glx_graph_destroy synchronises the device before it lets the work buffers go: nothing runs on `stream` / `side` any more
     for (int q = 0; q < 8; ++q) if (e_exec[q / 2][q % 2]) hipGraphExecDestroy(e_exec[q / 2][q % 2]);
-    for (int q = 0; q < 2; ++q) if (e_ev[q]) hipEventDestroy(e_ev[q]);
-    if (h_stage) hipHostFree(h_stage);
-    if (h_hist) hipHostFree(h_hist);
     for (int q = 0; q < 3; ++q) if (f_exec[q]) hipGraphExecDestroy(f_exec[q]);
+    for (int q = 0; q < 2; ++q) if (e_ev[q]) hipEventDestroy(e_ev[q]);
     for (int q = 0; q < 3; ++q) if (f_ev[q]) hipEventDestroy(f_ev[q]);
     if (side) hipStreamDestroy(side);
-    if (h_err) hipHostFree(h_err);
-    if (h_ss) hipHostFree(h_ss);
     if (stream) hipStreamDestroy(stream);
+    for (auto& kv : cap) {
+      if (!*kv.first) continue;
+      if (kv.second.host) hipHostFree(*kv.first); else hipFree(*kv.first);
+    }
   }
 };
 
@@ -152,6 +145,50 @@ size_t glx_seqsum_sum_doubles(int ncols, int nchunks, int which);
 int glx_seqsum_run(int mode, const double* prod, int64_t n, int ncols_all, int C, const CgScalars& sc, int it, double tol, const SsWork& w,
                    hipStream_t st);
 
+// ---- a solve: what its stages work on.  cg.hip (CgExact) and cg_fused.hip (CgFused) add their mode's own state ------------------------
+struct CgSolve {
+  glx_graph* A;
+  CgShape s;                      // n, C, Cg, padded columns, record length, max_iter, systems, Dirichlet rows (cg_plan.h)
+  double tol;
+  int flags, stride, dtype;
+  CgStop stop;
+  const CgRhsRows& rr;
+  CgBufs& b;                      // the operator's work buffers (A->cg_ws, made on its first solve)
+  hipStream_t st = nullptr;
+  RecLayout L;
+  SellPlan* plan = nullptr;
+  size_t recb = 0, denseb = 0;    // bytes of one of x, r, p, ap / of the caller's (n, C) array
+  int64_t nb_spmm = 1;
+  SweepArgs a;                    // the SpMM Ap = A p of every iteration
+  CgSolve(glx_graph* A_, int C, int Cg, double tol_, int64_t max_iter, int flags_, const CgRhsRows& rr_)
+      : A(A_), s{A_->n_rows, C, Cg, 0, 0, max_iter, C / Cg, 0}, tol(tol_), flags(flags_), stride(C / Cg + 1), dtype(A_->dtype),
+        stop(C / Cg, tol_), rr(rr_), b(*(CgBufs*)(A_->cg_ws ? A_->cg_ws : (A_->cg_ws = new CgBufs()))) {}
+};
+typedef int (*CgLimits)(const CgShape&, char*, size_t);
+// layout, plan (`relaxed`: the image whose row segments sum independently, graph.hip), the mode's limits, the operator's work buffers
+// with x r p ap dense scal in them, its stream, and what every iteration's SpMM is given in both modes
+int cg_open(CgSolve& c, bool relaxed, CgLimits limits, const int32_t* mask_rows, const int32_t* mask_ptr);
+// the caller's (n, C) array `host` as records in `rec` (caller row order -> the operator's)
+int cg_load_dense(CgSolve& c, const void* host, void* rec);
+// x as the caller's (n, C) array in X, every row times scale[row] (device; null: as it is); the stream drained; iterations and err per system
+int cg_finish(CgSolve& c, void* X, const double* scale, int* iters_out, double* err_out);
+
+// `enqueue()` captured on `st` into *exec.  On any failure the graph is destroyed, *exec is null and a GLX_* code comes back.
+template <class F> int cg_capture(hipStream_t st, hipGraphExec_t* exec, F&& enqueue) {
+  *exec = nullptr;
+  hipGraph_t graph = nullptr;
+  GLX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  const int rc = enqueue();
+  const hipError_t e = hipStreamEndCapture(st, &graph);
+  const hipError_t e2 = (!rc && e == hipSuccess) ? hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) : hipSuccess;
+  if (graph) hipGraphDestroy(graph);
+  if (rc) return rc;
+  GLX_HIP(e);
+  if (e2 != hipSuccess) *exec = nullptr;
+  GLX_HIP(e2);
+  return GLX_OK;
+}
+
 // the tolerance-mode solve (cg_fused.hip); arguments as cg.hip's cg_run
 int glx_cg_run_fused(glx_graph* A, const void* B, void* X, int C, int Cg, double tol, int64_t max_iter, int* iters_out, double* err_out,
                      int flags, const int32_t* mask_rows, const int32_t* mask_ptr, const CgRhsRows& rr);
@@ -159,3 +196,4 @@ int glx_cg_run_fused(glx_graph* A, const void* B, void* X, int C, int Cg, double
 int glx_cg_unpack_scaled(int dtype, const void* rec, void* dense, int64_t n, const RecLayout& L, const int32_t* perm, const double* scale,
                          hipStream_t st);
 #define CG_NEED(ptr, bytes) do { int rc_ = b.need((void**)&(ptr), (bytes)); if (rc_) return rc_; } while (0)
+#define CG_NEED_HOST(ptr, bytes) do { int rc_ = b.need_host(&(ptr), (bytes)); if (rc_) return rc_; } while (0)

@@ -91,6 +91,45 @@ def test_captured_chunks_equal_eager_launches(gl, orc, monkeypatch, n, C, max_it
     G.close()
 
 
+@pytest.mark.parametrize('n,name', [(9000, None), (300, 'blocks')])
+def test_modes_alternating_on_one_operator_equal_fresh_operators(gl, form, n, name):
+    """Both modes share one set of work buffers, and the tolerance mode's residual history is (max_iter + 66) rows against the
+    reference-order ring of 9: alternating them on ONE operator reallocates err_hist under launch sequences captured for the other
+    mode, and only the replay key keeps those from being replayed.  Every solve of the sequence returns, bit for bit (both modes are
+    deterministic), what the same call returns on a fresh operator: x, iterations, err.  n = 9000: the default block form and full
+    captured chunks; n = 300 with the block form forced."""
+    from graphlearning_amd import _hip
+    form(name)
+    rng = np.random.default_rng(n)
+    A = _spd(n, 5)
+    b4 = rng.normal(size=(n, 4)) * np.exp(rng.normal(size=4) * 2)
+    b1 = rng.normal(size=n)
+    B = rng.normal(size=(n, 6))
+    masks = [rng.choice(n, size=k, replace=False) for k in (0, n // 13, n // 3)]
+    exact4, tree4 = lambda G: G.cg(b4, 1e-9), lambda G: G.cg(b4, 1e-9, reduce='tree')
+    steps = [exact4, tree4, exact4,
+             lambda G: G.cg_groups(B, 2, masks=masks, reduce='tree'),
+             lambda G: G.cg_groups(B, 2, masks=masks),
+             lambda G: G.cg(b1, 1e-9),                                   # a 1-D right-hand side: the pairwise path
+             lambda G: G.cg(b4, 1e-6, reduce='tree', max_iter=40),
+             exact4]
+    fresh = {}
+    for step in steps:
+        if step not in fresh:                                            # (one fresh operator per distinct call)
+            G = _hip.DeviceGraph(A)
+            fresh[step] = step(G)
+            G.close()
+    G = _hip.DeviceGraph(A)
+    try:
+        for k, step in enumerate(steps):
+            got = step(G)
+            for q in range(3):
+                assert _same(got[q], fresh[step][q]), (k, q)
+    finally:
+        G.close()
+    assert fresh[exact4][1] > 8 and fresh[tree4][1] > 4        # whole captured chunks ran in both modes
+
+
 def test_block_form_with_the_prefix_scan_of_many_groups(gl, orc, form):
     """From 1024 groups of 1024 rows on, the approximate prefix in front of a group comes from a scan pass (ss_scan_kernel) instead of every
     workgroup adding all group sums in front of it (quadratic in the number of groups).  1.1 M rows, a few iterations: the same

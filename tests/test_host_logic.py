@@ -363,8 +363,9 @@ def test_captured_launch_sequences_hold_no_memset_node():
         'solver.hip: enqueue_head': body('solver.hip', 'static int enqueue_head(glx_sweep* s)', 'extern "C" int glx_sweep_run'),
         'solver.hip: launch_sweep': body('solver.hip', 'static int launch_sweep(', 'static int enqueue_head('),
         'groups.hip: grp_launch_sweep + grp_enqueue_head': body('groups.hip', 'static int grp_launch_sweep(', 'static double grp_err_value('),
-        'cg.hip: enqueue_iteration + enqueue_chunk': body('cg.hip', 'auto enqueue_iteration = ', '// Full chunks are replayed from a captured launch sequence'),
-        'cg_fused.hip: enqueue_chunk': body('cg_fused.hip', 'auto enqueue_chunk = ', 'hipStreamBeginCapture'),
+        'cg.hip: reduce': body('cg.hip', 'template <int MODE> int reduce(int i, bool blocks) {', '// x = x0 or 0, r = p = b'),
+        'cg.hip: enqueue_iteration + enqueue_chunk': body('cg.hip', 'int enqueue_iteration(int i, bool bl0, bool bl1) {', '// Full chunks are replayed from a captured launch sequence'),
+        'cg_fused.hip: enqueue_chunk': body('cg_fused.hip', 'int enqueue_chunk(int iters) {', '// the three chunk lengths as captured launch sequences'),
         'dist.hip: enqueue_reset .. enqueue_sweep helpers': body('dist.hip', 'static int enqueue_reset(', 'static int ensure_ring('),
     }
     for name, text in captured.items():
