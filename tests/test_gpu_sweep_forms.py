@@ -9,6 +9,7 @@ comparing the loop with `A @ u` in float64.  The device is held to equal bits.""
 import numpy as np
 import pytest
 from scipy import sparse
+from sweep_ref import host_sweep      # the entry-order loop (tests/test_sweep_ref_host.py holds it against scipy too)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,23 +38,6 @@ def _graph(seed):
     return A, lengths
 
 
-def _host_sweep(A, u, Db, dtype):
-    """Db + A u with every row summed entry by entry in stored order, product and sum rounded separately in `dtype`.  (Entry j of
-    all rows that have one is added in one numpy statement: the order inside every row is that of a loop over its entries.)"""
-    indptr, indices = A.indptr.astype(np.int64), A.indices
-    data = A.data.astype(dtype)
-    lengths = np.diff(indptr)
-    u = u.astype(dtype)
-    acc = np.zeros((A.shape[0], u.shape[1]), dtype=dtype)
-    for j in range(int(lengths.max())):
-        rows = np.nonzero(lengths > j)[0]
-        at = indptr[rows] + j
-        prod = u[indices[at]] * data[at][:, None]
-        acc[rows] = acc[rows] + prod
-    assert acc.dtype == dtype
-    return acc if Db is None else Db.astype(dtype) + acc
-
-
 @pytest.fixture(scope='module')
 def forms(gl):
     """The graph, its operands at the widest width, and one operator per dtype (every width's plan lives in it)."""
@@ -67,8 +51,8 @@ def forms(gl):
     rng = np.random.default_rng(12)
     u = rng.normal(size=(N, max(WIDTHS)))
     Db = rng.normal(size=(N, max(WIDTHS)))
-    assert np.array_equal(_host_sweep(A, u, None, np.float64), A @ u)                # the reference itself, against scipy
-    assert np.array_equal(_host_sweep(A, u, Db, np.float64), Db + A @ u)
+    assert np.array_equal(host_sweep(A, u, None, np.float64), A @ u)                # the reference itself, against scipy
+    assert np.array_equal(host_sweep(A, u, Db, np.float64), Db + A @ u)
     graphs = {dt: _hip.DeviceGraph(A, dtype=dt, keep_order=True) for dt in (np.float64, np.float32)}
     for G in graphs.values():
         assert np.array_equal(G.order(), np.arange(N)) and G.info()['max_row'] == max(LENGTHS)
@@ -87,7 +71,7 @@ def test_spmm_bias_equals_the_entry_order_loop(forms, C, dtype):
     for bias in (np.ascontiguousarray(Db[:, :C]).astype(dtype), None):
         ref = uc
         for iters in (1, 2):
-            ref = _host_sweep(A, ref, bias, dtype)
+            ref = host_sweep(A, ref, bias, dtype)
             got = G.spmm_bias(uc, bias, iters=iters)
             assert got.dtype == dtype and got.shape == (N, C)
             assert np.array_equal(got, ref), (C, np.dtype(dtype).name, bias is not None, iters)
