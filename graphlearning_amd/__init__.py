@@ -18,6 +18,7 @@ from .graph import graph          # like the reference: gl.graph(W) is the class
 from . import trainsets
 from . import weightmatrix
 from . import ssl
+from . import clustering
 from ._hip import GlxError
 
 __version__ = '0.1.0'

@@ -170,6 +170,12 @@ _SIGNATURES = {
     'glx_eig_rotate': [_vp, _vp, C.c_int, C.c_int],
     'glx_eig_get_columns': [_vp, C.c_int, C.c_int, _vp],
     'glx_eig_destroy': [_vp],
+    'glx_incres_set_options': [_vp],
+    'glx_incres_create': [C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
+    'glx_incres_step': [_vp, _vp, C.c_int64, C.c_int64, _vp, _i64p],
+    'glx_incres_stats': [_vp, _i64p],
+    'glx_incres_destroy': [_vp],
+    'glx_host_group_by_label': [C.c_int64, _vp, C.c_int, _vp, _vp],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1312,6 +1318,105 @@ class Eig:
             lib = load(required=False)
             if lib is not None:
                 lib.glx_eig_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def host_group_by_label(labels, k):
+    """(counts (k) int64, order (n) int32): the vertex ids sorted by label, ascending inside a label (glx_host_group_by_label, a
+    counting sort on the host; no device is touched).  GlxError for a label outside [0, k)."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    counts = np.empty(int(k), dtype=np.int64)
+    order = np.empty(len(labels), dtype=np.int32)
+    check(load().glx_host_group_by_label(len(labels), _ptr(labels), int(k), _ptr(counts), _ptr(order)), 'glx_host_group_by_label')
+    return counts, order
+
+
+class _IncresOptions(C.Structure):
+    _fields_ = [('chunk', C.c_int), ('margin', C.c_int), ('next', C.c_int)]
+
+
+class incres_options:
+    """Context manager: the schedule of the calling thread's INCRES grow loops (glx_incres_set_options) -- chunk: sweeps between two
+    reads of the flags, every chunk alike; margin: the first chunk of a loop is the count of the loop before plus this; next: the
+    length of a loop's second chunk, every further one twice as long (each 1 .. 64, None: the library decides).  Every schedule gives the same labels and counts; tests and
+    measurements use this."""
+
+    def __init__(self, chunk=None, margin=None, next=None):
+        self.opt = _IncresOptions(int(chunk or 0), int(margin or 0), int(next or 0))
+
+    def __enter__(self):
+        check(load().glx_incres_set_options(C.byref(self.opt)), 'glx_incres_set_options')
+        return self
+
+    def __exit__(self, *exc):
+        load().glx_incres_set_options(None)
+        return False
+
+
+class Incres:
+    """The device half of clustering.incres (glx_incres_*, csrc/incres.hip; the contract is DESIGN.md 4.15): the transition matrix P
+    as CSR arrays whose rows keep their STORED order (scipy's `W*D`, unsorted, as it is) and a state of k columns that stays on the
+    device.  step(seeds, max_grow) plants the (k, m) seeds, grows until no entry of the state is zero and returns (labels (n) int32,
+    sweeps).  A context manager; close() releases the device memory.  GlxError on every refusal of the library, the cap on the sweeps
+    included; the object stays usable after it (`last_sweeps` then holds the cap)."""
+
+    def __init__(self, row_ptr, col, val, k, device=None):
+        self._h = _vp()
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        n = len(row_ptr) - 1
+        if row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or val.shape != col.shape or int(row_ptr[0]) != 0 or int(row_ptr[-1]) != len(col):
+            raise GlxError('Incres: inconsistent array shapes or sizes')
+        self.n, self.k = n, int(k)
+        self.last_sweeps = None
+        check(load().glx_incres_create(n, _ptr(row_ptr), _ptr(col), _ptr(val), int(k), _dev(device), C.byref(self._h)), 'glx_incres_create')
+
+    def _handle(self):
+        if not self._h.value:
+            raise GlxError('Incres: the object is closed')
+        return self._h
+
+    def step(self, seeds, max_grow=None, out=None):
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        if seeds.ndim != 2 or seeds.shape[0] != self.k or seeds.shape[1] < 1:
+            raise GlxError('Incres.step: seeds of shape %s, expected (%d, m >= 1)' % (seeds.shape, self.k))
+        labels = pinned_empty((self.n,), np.int32) if out is None else out
+        if labels.dtype != np.int32 or labels.shape != (self.n,) or not labels.flags.c_contiguous:
+            raise GlxError('Incres.step: out must be a contiguous int32 array of %d entries' % self.n)
+        sweeps = C.c_int64(-1)
+        self.last_sweeps = None
+        rc = load().glx_incres_step(self._handle(), _ptr(seeds), seeds.shape[1], int(2 * self.n + 2 if max_grow is None else max_grow),
+                                    _ptr(labels), C.byref(sweeps))
+        self.last_sweeps = int(sweeps.value)
+        check(rc, 'glx_incres_step')
+        return labels, int(sweeps.value)
+
+    def stats(self):
+        """dict: chunk_cap, first_chunk, margin, next_chunk, loops, chunks, enqueued, counted, lanes, record, renumbered, slices"""
+        out = (C.c_int64 * 12)()
+        check(load().glx_incres_stats(self._handle(), out), 'glx_incres_stats')
+        names = ('chunk_cap', 'first_chunk', 'margin', 'next_chunk', 'loops', 'chunks', 'enqueued', 'counted', 'lanes', 'record', 'renumbered',
+                 'slices')
+        return dict(zip(names, (int(v) for v in out)))
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            lib = load(required=False)
+            if lib is not None:
+                lib.glx_incres_destroy(self._h)
             self._h = _vp()
 
     def __enter__(self):

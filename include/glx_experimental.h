@@ -315,6 +315,37 @@ int glx_eig_rotate(glx_eig* e, const double* Y, int rows, int keep);
 int glx_eig_get_columns(glx_eig* e, int j0, int j1, double* out);
 int glx_eig_destroy(glx_eig* e);
 
+/* ---- INCRES clustering: clustering.incres (csrc/incres.hip, csrc/incres_plan.h) -----------------------------------------------------
+ * The device half of one outer iteration of the reference's clustering.incres (clustering.py:348-361; Bresson et al. 2016): plant,
+ * grow `while np.min(F) == 0: F = P*F`, harvest `np.argmax(F, axis=1)`.  The handle holds P (n x n, CSR with int32 row pointers; a
+ * row's STORED entry order is kept and is the order of every sum: hand over scipy's `W*D` as it is, unsorted) and the state of k <= 256
+ * columns across the iterations.  The product is the sweep engine's, bit for bit scipy's csr_matvecs; the census behind every sweep
+ * tests the k real columns for an entry equal to 0.0 (a denormal is not zero) and takes the row-wise first-maximum index.  The contract
+ * is DESIGN.md 4.15.  OWNERSHIP: the caller owns *out and releases it with glx_incres_destroy.  All pointers are host pointers; every
+ * call returns with its work complete.
+ * glx_incres_step: seeds (k, m) row-major, vertex ids in the caller's numbering, duplicates allowed: F <- 0, F[seeds[r][:], r] <- 1;
+ *   then sweeps until no entry is zero; labels_out (n) <- the argmax, *sweeps_out <- the number of sweeps (0: the planted state had no
+ *   zero).  At most max_grow sweeps: GLX_EUNSUPPORTED if the iterate behind max_grow sweeps still holds a zero (*sweeps_out = max_grow;
+ *   the graph is disconnected, bipartite, or so long that values underflow) -- an error return, the handle stays usable.
+ * glx_incres_stats: out[12] <- the chunk cap, the first guess, the margin, the length of a loop's second chunk, grow loops so far, chunks read,
+ *   sweeps enqueued, sweeps counted, lanes per record, elements per record, 1 if the locality renumbering is in use, slices.
+ * glx_host_group_by_label (host only, no device): the vertices grouped by label for the plant's draws -- counts (k) <- members per label,
+ *   order (n) <- the vertex ids sorted by label, ascending inside a label (a counting sort): the members of cluster r in ascending
+ *   order are order[counts[0] + .. + counts[r-1] ..][:counts[r]].  GLX_EINVAL: a label outside [0, k).
+ * glx_incres_set_options: the calling thread's schedule -- chunk: every chunk has this length; margin: the first chunk of a loop is the
+ *   count before plus this; next: the length of a loop's second chunk, every further one twice the one before (each 1 .. 64; 0, or
+ *   NULL for all: the library decides).  No result
+ *   depends on them.
+ * GLX_EINVAL: a null argument, n < 1, an index or a seed out of range, m or max_grow below 1.  GLX_EUNSUPPORTED: k outside 1 .. 256. */
+typedef struct glx_incres glx_incres;
+typedef struct { int chunk, margin, next; } glx_incres_options;
+int glx_incres_set_options(const glx_incres_options* opt);
+int glx_incres_create(int64_t n, const int32_t* row_ptr, const int32_t* col, const double* val, int k, int device, glx_incres** out);
+int glx_incres_step(glx_incres* h, const int32_t* seeds, int64_t m, int64_t max_grow, int32_t* labels_out, int64_t* sweeps_out);
+int glx_incres_stats(glx_incres* h, int64_t* out);
+int glx_incres_destroy(glx_incres* h);
+int glx_host_group_by_label(int64_t n, const int32_t* labels, int k, int64_t* counts, int32_t* order);
+
 #ifdef __cplusplus
 }
 #endif
