@@ -56,6 +56,25 @@ KNN_HOST_DEVICE inline double knn_filter_scale(double rmax) {
   return scale;
 }
 
+// ---- the margin of the re-rank's acceptance test -----------------------------------------------------------------------------------
+// A row is accepted when every full list's threshold tau satisfies tau >= dk2 + 2 eps: then every ref r the filter rejected (filter
+// value >= tau) is at least as far as the k-th candidate (exact squared distance dk2, here in the filter's units).  The filter's error
+// on a pair is bounded PER PAIR: every term of the derivation of cerr (knn_make_plan) is a multiple of |q||r|, |q|^2 or |r|^2, so
+// |filter - exact| <= E(r) with E(r) < 2 cerr (|q| + |r|)^2, and (|q| + rmax)^2 is only its largest value.  The rejected refs come in
+// two kinds.  |r| > |q| + dk: the triangle inequality alone puts r farther than dk, whatever the filter said.  |r| <= R := min(rmax,
+// |q| + dk): exact >= tau - E(r) >= tau - 2 cerr (|q| + R)^2.  So eps = cerr (|q| + R)^2 serves, with R taken 2^-10 larger for the
+// fp32 norms, plus 2^-12 of the old eps for the absolute errors of underflowing products (knn_filter_scale, above: U is 2^-12 of
+// cerr rmax^2 at worst).  For a query far from every ref (dk >= rmax - |q|) this is the old margin cerr (|q| + rmax)^2; for data of
+// low intrinsic dimension, where neighbours are close compared with the cloud's radius, it is what keeps the short lists' thresholds
+// outside the margin: N(0, 1) data in one dimension, n = 2999, k = 12 sent 1267 rows to the exact fallback with the old margin
+// (tests/test_gpu_knn_narrow.py), 4 with this one.
+KNN_HOST_DEVICE inline double knn_accept_eps(double cerr, double qnorm, double rmax, double dk2s) {
+  const double far = qnorm + rmax;
+  const double R = fmin(rmax, (qnorm + sqrt(dk2s)) * (1.0 + 0x1p-10));
+  const double near = qnorm + R;
+  return cerr * near * near + 0x1p-12 * cerr * far * far;
+}
+
 // features per half per block of the blocked (d > 130) fp32 variant; 16 where the KP = 64 lists leave less LDS
 constexpr int knn_kb(int KP) { return KP == 64 ? 16 : 32; }   // (KP = 8 never takes the blocked variant)
 

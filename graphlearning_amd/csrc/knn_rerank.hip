@@ -177,11 +177,12 @@ __global__ __launch_bounds__(64) void knn_rerank_kernel(const double* __restrict
   // (tau and eps0 are in the filter's units, dk2 is exact and in the data's: knn_plan.h, knn_filter_scale; the scale is applied twice
   // since its square may leave fp64's range)
   const double fsc = knn_scale_of(rmax_p), dk2s = dk2 * fsc * fsc;
+  const double eps1 = knn_accept_eps(cerr, (double)qnorm[q], (double)rmax_p[0], dk2s);   // (<= eps0 (1 + 2^-12): knn_plan.h)
   int bad = 0;
   for (int l = lane; l < lists; l += 64) {
     float tau = 0.f;
     for (int p = 0; p < KP; ++p) tau = fmaxf(tau, cand_d[ql * ncand + l * KP + p]);
-    if (tau < INFINITY && !((double)tau >= dk2s + 2.0 * eps0)) bad = 1;
+    if (tau < INFINITY && !((double)tau >= dk2s + 2.0 * eps1)) bad = 1;
   }
   bad = __any(bad) || !(dk2 < INFINITY);
   if (lane == 0) {
@@ -502,7 +503,7 @@ __device__ __forceinline__ void lds_sort_pairs(double* sd, int* si, int P) {
 // One workgroup per query of the chunk [q_begin, q_begin + nq) of a pass that started at q_pass.  The same rule as knn_rerank_kernel:
 // with v_k the k-th smallest filter value, only candidates within v_k + 4 eps can be among the k nearest; those get exact fp64
 // distances (sqdist_exact), are sorted by (distance, caller index), and the first k go out.  The acceptance test is unchanged: every
-// full list's threshold must be at least dk2 + 2 eps.  flags / dk2_out / badrows are indexed by the row within the PASS (the
+// full list's threshold must be at least dk2 + 2 eps (eps of knn_accept_eps).  flags / dk2_out / badrows are indexed by the row within the PASS (the
 // fallback's numbering); cand_d / cand_i by the row within the chunk.  LDS: M * 16 bytes (64 KB at M = 4096).
 __global__ __launch_bounds__(256) void knn_rerank_wide_kernel(const double* __restrict__ X, int64_t n, int d, int k, int64_t q_begin, int64_t nq,
                                                               int64_t q_pass, const float* __restrict__ cand_d, const int* __restrict__ cand_i,
@@ -563,11 +564,12 @@ __global__ __launch_bounds__(256) void knn_rerank_wide_kernel(const double* __re
   }
   const double dk2 = sd[k - 1];
   const double fsc = knn_scale_of(rmax_p), dk2s = dk2 * fsc * fsc;       // (the filter's units, as in knn_rerank_kernel)
+  const double eps1 = knn_accept_eps(cerr, (double)qnorm[q], (double)rmax_p[0], dk2s);
   int bad = 0;
   for (int l = tid; l < lists; l += 256) {
     float tau = 0.f;
     for (int p = 0; p < KP; ++p) tau = fmaxf(tau, cd[l * KP + p]);
-    if (tau < INFINITY && !((double)tau >= dk2s + 2.0 * eps0)) bad = 1;
+    if (tau < INFINITY && !((double)tau >= dk2s + 2.0 * eps1)) bad = 1;
   }
   bad = __syncthreads_or(bad) || !(dk2 < INFINITY);
   if (tid == 0) {

@@ -4,6 +4,11 @@
 //                    and the decision either side of it and of 64 | 65), F rows (the wide fallback's sizes)
 //   chain FILE M D   knn_chain_places of the M x D doubles in FILE: the places, one line
 //   scale R ...      knn_filter_scale of every R (hex floats welcome): one "%a" per line
+//   accept_eps CERR QNORM RMAX DK2S
+//                    knn_accept_eps, the margin of the re-rank's acceptance test: one "%a"
+//   plan N D K NQ LONG FILTER LISTS NSPLIT CONCAT
+//                    the plan of one case under the overrides {FILTER, LISTS, NSPLIT, CONCAT} (glx_knn_options' numbers), one row in the
+//                    format of `plans`; D and K may be ranges LO:HI (inclusive): one row per (d, k), d outermost
 // The row formats are those of the table recorded in tests/golden/knn_plans.txt.
 #include "knn_plan.h"
 #include <cstdio>
@@ -101,6 +106,25 @@ static int chain(const char* path, int m, int d) {
   return 0;
 }
 
+static void range(const char* s, int* lo, int* hi) {
+  *lo = *hi = atoi(s);
+  if (const char* c = strchr(s, ':')) *hi = atoi(c + 1);
+}
+
+static int plan(char** a) {
+  int d0, d1, k0, k1;
+  range(a[1], &d0, &d1);
+  range(a[2], &k0, &k1);
+  const int64_t n = atoll(a[0]), nq = atoll(a[3]);
+  g_opt = {atoi(a[5]), atoi(a[6]), atoi(a[7]), atoi(a[8])};
+  if (n < 1 || nq < 1 || d0 < 1 || k0 < 1 || g_opt.filter < 0 || g_opt.filter > 2 || g_opt.lists < 0 || g_opt.lists > 2 || g_opt.nsplit < 0 ||
+      g_opt.nsplit > 32 || g_opt.concat < -1 || g_opt.concat > 2)
+    return 2;
+  for (int d = d0; d <= d1; ++d)
+    for (int k = k0; k <= k1; ++k) plan_row(n, d, k, nq, atoi(a[4]) != 0);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "plans")) { plans(); return 0; }
   if (argc == 2 && !strcmp(argv[1], "extras")) { extras(); return 0; }
@@ -109,6 +133,11 @@ int main(int argc, char** argv) {
     for (int a = 2; a < argc; ++a) printf("%a\n", knn_filter_scale(strtod(argv[a], nullptr)));
     return 0;
   }
-  fprintf(stderr, "usage: knn_plan_host plans | extras | chain FILE M D | scale R ...\n");
+  if (argc == 6 && !strcmp(argv[1], "accept_eps")) {
+    printf("%a\n", knn_accept_eps(strtod(argv[2], nullptr), strtod(argv[3], nullptr), strtod(argv[4], nullptr), strtod(argv[5], nullptr)));
+    return 0;
+  }
+  if (argc == 11 && !strcmp(argv[1], "plan")) return plan(argv + 2);
+  fprintf(stderr, "usage: knn_plan_host plans | extras | chain FILE M D | scale R ... | accept_eps CERR QNORM RMAX DK2S | plan N D K NQ LONG FILTER LISTS NSPLIT CONCAT\n");
   return 2;
 }

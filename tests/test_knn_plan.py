@@ -179,3 +179,115 @@ def test_scale_of_the_filters_operands(driver):
         assert np.isfinite(s) and s >= 2.0 ** -1022
     nothing = [0.0, 5e-324, 2.0 ** -1023, 2.0 ** 1023, float('inf'), float('nan')]
     assert scales(nothing) == [1.0] * len(nothing)
+
+
+# ---- the coverage census of the narrow search (k <= 60): tests/knn_narrow_cases.py against the header ---------------------------------
+def _plan_rows(out):
+    import knn_narrow_cases as nc
+    for row in out.split('\n'):
+        if row:
+            (n, d, k, nq, long_lists, _, _), q = parse(row)
+            yield (n, d, k, nq, long_lists), nc.Plan(q['KP'], q['DH'], q['nkb'], q['NKB'], q['dpa'], q['BR'], q['ntiles'], q['nsplit'], bool(q['use_bf16']),
+                                                     q['cat'], bool(q['short_lists']))
+
+
+@pytest.fixture(scope='module')
+def census(driver):
+    """Every plan of d = 1 .. 400 x k = 1 .. 60 x filter {default, f32} x lists {default, long} at the n of the GPU cases:
+    {kernel key: a (d, k, filter, lists) that takes it}; the Python restatement must give the header's plan at every point, for the
+    escalated pass (long_lists = 1) as well."""
+    import knn_narrow_cases as nc
+    keys = {}
+    for filt in (None, 'f32'):
+        for lists in (None, 'long'):
+            for long_lists in (0, 1):
+                out = driver('plan', nc.N_MAIN, '1:400', '1:60', nc.N_MAIN, long_lists, nc.FILTER[filt], nc.LISTS[lists], 0, -1)
+                rows = list(_plan_rows(out))
+                assert len(rows) == 400 * 60
+                for (n, d, k, nq, ll), p in rows:
+                    assert p == nc.plan(n, d, k, nq, bool(ll), filter=filt, lists=lists), (d, k, filt, lists, ll)
+                    if not long_lists:
+                        keys.setdefault(nc.kernel_key(p), (d, k, filt, lists))
+    return keys
+
+
+def test_narrow_cases_reach_every_tile_kernel(census):
+    """Every instantiation of the two tile kernels that some (d, k, filter, lists) with k <= 60 launches is launched by a case of
+    tests/test_gpu_knn_narrow.py's main matrix (n = 2999).  A tile class added to the plan without a case fails here."""
+    import knn_narrow_cases as nc
+    # bf16: NKB 1, 2 (three operand forms), 4, 6, 8 x lists of 8, 16, 32; fp32: DH 8, 12, 18, 34, 66 x lists of 8, 16, 32, lists of 64
+    # at DH 8, 12, 18, and the blocked variant with DH = 32 (lists of 16, 32) and 16 (lists of 64)
+    assert len(census) == 7 * 3 + 5 * 3 + 3 + 3, sorted(census)
+    hit = {}
+    for c in nc.CASES:
+        if c.n == nc.N_MAIN and c.group in ('main', 'f32', 'long'):
+            hit.setdefault(nc.kernel_key(nc.case_plan(c)), nc.case_id(c))
+    missing = {key: where for key, where in census.items() if key not in hit}
+    assert not missing, 'tile kernels no case runs (key: a d, k, filter, lists that takes it): %s' % missing
+    assert set(hit) == set(census)           # (and no case claims a key the plan never produces)
+
+
+def test_narrow_case_table_is_the_issued_one():
+    import knn_narrow_cases as nc
+    by = {}
+    for c in nc.CASES:
+        by.setdefault(c.group, []).append(c)
+    main = by['main']
+    assert {(c.d, c.k) for c in main if c.style == 'iso'} == {(d, k) for d in nc.MAIN_D for k in nc.MAIN_K}
+    for d in nc.MAIN_D:
+        adv = {c.k: c.style for c in main if c.d == d and c.style != 'iso'}
+        assert sorted(adv) == [12, 29] and all(s in nc.ADVERSARIAL or (s == 'grid' and d <= 3) for s in adv.values()), (d, adv)
+    for lo, hi in ((1, 16), (17, 32), (33, 64), (65, 96), (97, 128)):           # every NKB class meets near-duplicates and an offset
+        styles = {c.style for c in main if lo <= c.d <= hi}
+        assert {'neardup', 'offset'} <= styles, (lo, hi, styles)
+    assert {(c.d, c.k) for c in by['f32']} == {(d, k) for d in (14, 15, 22, 23, 34, 35, 66, 67, 128) for k in nc.MAIN_K}
+    assert {(c.d, c.k) for c in by['long']} >= {(d, k) for d in (20, 33, 64, 96, 130, 190, 191) for k in (12, 28, 29, 60)}
+    assert all(dict(c.opts) == {'filter': 'f32'} for c in by['f32']) and all(dict(c.opts) == {'lists': 'long'} for c in by['long'])
+    assert {(c.d, c.k, c.opts) for c in by['repair']} >= {(d, 12, (('nsplit', 1),)) for d in (96, 128)}
+    assert {(c.d, c.k, c.style) for c in by['split']} == {(d, k, 'lohalf') for d in (32, 64, 96, 128) for k in (12, 29)}
+    assert {(c.d, c.n, c.k) for c in by['small']} == {(d, n, k) for d in (21, 96, 128, 130) for n, k in ((60, 60), (33, 12), (129, 29))}
+    assert len({nc.case_id(c) for c in nc.CASES}) == len(nc.CASES)
+
+
+def test_every_narrow_case_plans_as_the_header_does(driver):
+    """Case by case, with the case's own n and overrides: the restatement the GPU test takes its expected statistics from is the
+    header's plan, for the first pass and for the long-list repeat."""
+    import knn_narrow_cases as nc
+    for c in nc.CASES:
+        o = dict(c.opts)
+        for long_lists in (0, 1):
+            out = driver('plan', c.n, c.d, c.k, c.n, long_lists, nc.FILTER[o.get('filter')], nc.LISTS[o.get('lists')], o.get('nsplit', 0), -1)
+            (_, p), = _plan_rows(out)
+            assert p == nc.case_plan(c, bool(long_lists)), (nc.case_id(c), long_lists)
+    # the classes the issue names, spelled out once
+    want = {(96, 12): ('bf16', 6, 0, 8, 32), (128, 28): ('bf16', 8, 0, 16, 32), (21, 12): ('bf16', 2, 1, 8, 64), (20, 60): ('bf16', 2, 2, 32, 32),
+            (22, 13): ('bf16', 2, 0, 16, 64), (130, 12): ('f32', 66, 8, False, 32), (131, 60): ('f32', 16, 64, True, 32)}
+    for (d, k), key in want.items():
+        assert nc.kernel_key(nc.plan(nc.N_MAIN, d, k)) == key, (d, k)
+
+
+def test_margin_of_the_acceptance_test(driver):
+    """knn_accept_eps = cerr (|q| + R)^2 + 2^-12 cerr (|q| + rmax)^2 with R = min(rmax, (|q| + dk) (1 + 2^-10)): never above the
+    uniform margin cerr (|q| + rmax)^2 by more than its 2^-12 floor, equal to it (plus the floor) once |q| + dk reaches rmax, never
+    below the pair bound cerr (|q| + |r|)^2 of any ref the triangle inequality does not exclude (|r| <= |q| + dk), growing with dk."""
+    def eps(cerr, q, rmax, dk2):
+        return float.fromhex(driver('accept_eps', float(cerr).hex(), float(q).hex(), float(rmax).hex(), float(dk2).hex()).strip())
+    rng = np.random.default_rng(8)
+    cerr = float.fromhex('0x1.3ap-15')
+    for _ in range(200):
+        rmax = float(np.ldexp(rng.uniform(1, 2), int(rng.integers(-40, 41))))
+        q = rmax * float(rng.uniform(0, 1))
+        dk = rmax * float(10.0 ** rng.uniform(-6, 0.5))
+        old = cerr * (q + rmax) ** 2
+        e = eps(cerr, q, rmax, dk * dk)
+        R = min(rmax, (q + dk) * (1 + 2.0 ** -10))
+        want = cerr * (q + R) * (q + R) + 2.0 ** -12 * cerr * (q + rmax) * (q + rmax)
+        assert abs(e - want) <= 1e-15 * want          # (a host compiler may contract the products and sums)
+        assert e <= old * (1 + 2.0 ** -12) * (1 + 1e-15)
+        if q + dk >= rmax:
+            assert e >= old * (1 - 1e-15)
+        r = min(rmax, q + dk)                       # the farthest ref the triangle inequality leaves in play
+        assert e >= cerr * (q + r) ** 2 * (1 - 1e-15)
+        assert eps(cerr, q, rmax, 4 * dk * dk) >= e
+    assert abs(eps(cerr, 1.0, 3.0, float('inf')) / (cerr * 16.0 * (1 + 2.0 ** -12)) - 1) <= 1e-15
+    assert abs(eps(cerr, 0.0, 3.0, 0.0) / (2.0 ** -12 * cerr * 9.0) - 1) <= 1e-15          # the floor: absolute errors of underflowing products
