@@ -16,7 +16,8 @@ from test_gpu_fuzz import _virtual_ranks_sweep, _ulps
 pytestmark = pytest.mark.gpu
 
 KERNELS = ['uniform', 'gaussian', 'symgaussian', 'distance', 'singular']
-ROW_CAP = 1024           # csrc/assemble.hip: the most one wavefront merges in LDS
+ROW_CAP = 1024           # csrc/assemble_plan.h: the most one wavefront merges in LDS (repeated here on purpose: the censuses below
+                         # are counted independently of the header; tests/test_assemble_host.py ties the two together)
 HUB_FLOOR = 2048         # the smallest global scratch of a hub row
 
 
@@ -221,6 +222,56 @@ def test_boundary_rows_with_the_device_exp(gl, orc, K, n, device_exp):
                 assert np.allclose(W.data, Wo.data, rtol=1e-15, atol=0), (K, kernel, worst)
             else:
                 assert worst <= (2 if symmetrize else 1), (K, kernel, symmetrize, worst)
+
+
+BLOCK_CENSUS = {        # K: (smallest M, largest M, rows with M <= 64, with 64 < M <= ROW_CAP, with M > ROW_CAP)
+    32: (63, 65, 699, 1, 0),
+    65: (128, 1429, 0, 1299, 1),
+    512: (1023, 1025, 0, 1499, 1),
+    1024: (2047, 2049, 0, 0, 2600),
+}
+
+
+def _block_lists(K, n, mutual):
+    """Circulant lists with one redirect (K = 65: and a vertex that everyone lists), given weights, and the census of the rows."""
+    ind, _ = _circulant(n, K, 60 + K, mutual)
+    _redirect(ind, n // 3, K // 2, 3)
+    if K == 65:
+        ind[:, K - 2] = 700
+    w = np.random.default_rng(K + mutual).random((n, K)) + 0.25
+    M = _census(ind, K)
+    census = (int(M.min()), int(M.max()), int(np.sum(M <= 64)), int(np.sum((M > 64) & (M <= ROW_CAP))), int(np.sum(M > ROW_CAP)))
+    return ind, w, census
+
+
+@pytest.mark.parametrize('mutual', [False, True])
+@pytest.mark.parametrize('K,n', [(32, 700), (65, 1300), (512, 1500), (1024, 2600)])
+def test_block_assembly_at_every_row_class(K, n, mutual):
+    """A rank's block of rows (glx_knn_rows_to_csr, row_base != 0: dist_build.assemble_rows_device) where the rows are register
+    rows with one longer one (K = 32), wavefront rows under the k > 64 host branch with a hub (65), rows at the wavefront cap with
+    a hub (512) and hubs at the scratch boundary (1024): identical to the scipy expressions on the block
+    (dist_build.assemble_rows) and to the rows of the whole matrix, for unequal blocks, both rules and unsymmetrised."""
+    from graphlearning_amd import dist_build, _hip
+    _hip.require_device()
+    ind, w, census = _block_lists(K, n, mutual)
+    assert census == BLOCK_CENSUS[K], census
+    bounds = np.array([0, n // 5, n // 2, n], dtype=np.int64)
+    msgs = [dist_build.reverse_messages(ind[bounds[r]:bounds[r + 1]], w[bounds[r]:bounds[r + 1]], int(bounds[r]), bounds) for r in range(3)]
+    for rule, sym in (('mean', 1), ('max', 2), (None, 0)):
+        whole = _hip.knn_to_csr(ind, None, K, kernel='given', sym=sym, weights=w)
+        for me in range(3):
+            lo, hi = int(bounds[me]), int(bounds[me + 1])
+            received = [msgs[r][me] for r in range(3)] if rule else None
+            args = (lo, hi, n, ind[lo:hi], w[lo:hi], received, rule is not None, rule or 'mean')
+            ref = dist_build.assemble_rows(*args)
+            got = dist_build.assemble_rows_device(*args, device=0)
+            tag = (K, mutual, rule, me)
+            assert got.shape == ref.shape == (hi - lo, n), tag
+            assert np.array_equal(got.indptr, ref.indptr) and np.array_equal(got.indices, ref.indices), tag
+            assert np.array_equal(got.data, ref.data), tag
+            rows = whole[lo:hi]
+            assert np.array_equal(got.indptr, rows.indptr) and np.array_equal(got.indices, rows.indices), tag
+            assert np.array_equal(got.data, rows.data), tag
 
 
 # ---- 2. weight matrices of real wide graphs, both entry routes -------------------------------------------------------------------------
