@@ -703,12 +703,6 @@ static int exchange_selftest(glx_dist_sweep* s) {
   return GLX_OK;
 }
 
-static double shard_max(const unsigned long long* h, int64_t t) {
-  unsigned long long m = 0;
-  for (int k = 0; k < ERR_SHARDS; ++k) m = std::max(m, h[(size_t)t * ERR_SHARDS + k]);
-  return __builtin_bit_cast(double, m);
-}
-
 // make err[t0 .. t0+cnt) global (max over ranks) and bring it to the host
 static int global_err(glx_dist_sweep* s, int64_t t0, int64_t cnt) {
   unsigned long long* p = s->err + (size_t)t0 * ERR_SHARDS;
@@ -772,7 +766,7 @@ extern "C" int glx_poisson_sweep_dist(glx_dist_sweep* s, int min_iter, int max_i
     if (head_err) {
       rc = global_err(s, 0, 1);
       if (rc) return rc;
-      err_T = shard_max(s->h_err, 0);
+      err_T = stop_value(s->h_err, ERR_SHARDS);
     }
     const int R = check_every + 1;
     while (T < max_iter && err_T > s->thresh) {   // a NaN error ends the loop like `nan > 1/n` (ssl.py:667)
@@ -793,7 +787,7 @@ extern "C" int glx_poisson_sweep_dist(glx_dist_sweep* s, int min_iter, int max_i
       if (rc) return rc;
       int q = 1;
       for (; q <= cnt; ++q) {
-        err_T = shard_max(s->h_err, q);
+        err_T = stop_value(s->h_err + (size_t)q * ERR_SHARDS, ERR_SHARDS);
         if (!(err_T > s->thresh)) break;
       }
       if (q > cnt) q = cnt;             // no stop inside the chunk: go on from its last iterate
@@ -951,7 +945,7 @@ extern "C" int glx_dist_sweep_interior(glx_dist_sweep* s, int want_err, double* 
   if (want_err) {
     GLX_HIP(hipMemcpyAsync(s->h_err, s->err, ERR_SHARDS * 8, hipMemcpyDeviceToHost, s->stream));
     GLX_HIP(hipStreamSynchronize(s->stream));
-    if (err_local_out) *err_local_out = shard_max(s->h_err, 0);
+    if (err_local_out) *err_local_out = stop_value(s->h_err, ERR_SHARDS);
   } else {
     GLX_HIP(hipStreamSynchronize(s->stream));
   }

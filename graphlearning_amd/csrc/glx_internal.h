@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "../../include/glx_experimental.h"   // (includes glx.h)
+#include "sweep_stop_plan.h"
 
 // wavefronts (= slices) per workgroup of the SpMM kernel
 #ifndef GLX_WPB
@@ -451,4 +452,67 @@ int glx_onehot_device(const long long* d_labels, void* dense_dev, int dtype, int
 int glx_project_scores(glx_projector** pp, int64_t n, int C, hipStream_t st, double** scores_out);
 int glx_onehot_records(const long long* d_labels, void* rec, int dtype, int64_t n, const RecLayout& L, const int32_t* perm, hipStream_t st);
 void glx_projector_destroy(glx_projector* p);
+
+// ---- sweep_core.hip: what glx_sweep (solver.hip) and glx_sweep_groups (groups.hip) share ----------------------------------------------
+// One prepared sweep on an operator: B column groups of C columns (the single form: B = 1), its buffers from the pool, and the driver
+// of the stop test.  Both objects derive from it and add their head policy and their launch graphs.
+struct SweepCore {
+  glx_graph* P = nullptr;
+  int device = 0;                           // copied from P: destruction must not touch the operator (it may already be gone)
+  int C = 0, B = 1, shards = 0;             // columns per group, groups, maxima per group and stop row
+  int min_iter = 0, max_iter = 0;
+  bool has_w = false, bias_set = false;     // stop column in the record; does a launch read the bias?
+  RecLayout L;
+  SellPlan* plan = nullptr;
+  int64_t n_rows = 0, n_cols = 0;
+  void* buf[2] = {nullptr, nullptr};        // the two iterates
+  void* bias = nullptr;
+  uint8_t* slot_has_bias = nullptr;
+  double *deg = nullptr, *vinf = nullptr;
+  double* w0 = nullptr;                     // [B][n_cols] stop values of the start, caller order
+  unsigned long long* err = nullptr;        // [max_iter + 1][B][shards]
+  unsigned long long* h_err = nullptr;      // page-locked mirror
+  void* dense = nullptr;                    // (n, C) staging of one group, at least two fp64 vectors
+  void* stage = nullptr;                    // device staging of a training set's rows
+  size_t stage_cap = 0;
+  glx_work* work = nullptr;                 // stream + events of this sweep, from the per-device list of idle sets
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  glx_projector* proj = nullptr;            // label decision on the device-resident state
+  int cur = 0;
+  double thresh = 0.0;                      // `> 1/n`, ssl.py:667
+  int64_t launches = 0;
+  StopWalk walk;                            // of the last run
+  size_t rec_bytes() const { return (size_t)L.ld * L.esize; }
+  size_t err_row() const { return (size_t)B * shards; }
+  int64_t nslots() const { return plan->nslices * plan->R; }
+};
+// plan, work set and buffers for layout L (iterates and bias zeroed in the sweep's stream); stop: with deg, vinf, w0, err and its
+// mirror.  After a failure the caller destroys the object as usual.
+int glx_sweep_core_create(SweepCore* c, glx_graph* P, const RecLayout& L, int C, int B, int shards, int min_iter, int max_iter, bool stop);
+// (the caller has synchronised the stream and destroyed its launch graphs)
+void glx_sweep_core_destroy(SweepCore* c);
+// deg, vinf (caller order) into record order; complete on return
+int glx_sweep_set_vectors_core(SweepCore* c, const double* deg, const double* vinf);
+// *block holds at least `need` bytes afterwards.  Growing synchronises the stream first -- stream work may still read the old block,
+// and the pool hands it on at once -- and allocates 2 x need.
+int glx_sweep_reserve(SweepCore* c, void** block, size_t* cap, size_t need);
+int glx_bias_flags_async(const SellPlan* plan, const void* bias, int rec_bytes, uint8_t* flags, hipStream_t st);
+// rows[q] of the bias, columns col0 .. col0 + C - 1 <- vals[q] (null: 0); w0_b (may be null) at rows[q] <- w0_rows[q] (null: 0).
+// All device pointers; rows in the caller's numbering.
+int glx_sweep_scatter_rows(SweepCore* c, const int64_t* rows, const void* vals, const double* w0_rows, double* w0_b, int64_t m, int col0);
+// sweep t: buf[cur] -> buf[cur ^ 1], cur flips, launches counts
+int glx_sweep_launch(SweepCore* c, int t, bool with_stop, unsigned used_mask);
+// what enqueue() puts into the sweep's stream, as a launch graph; cur and launches are left as they were (nothing has run)
+int glx_sweep_capture(SweepCore* c, const std::function<int()>& enqueue, hipGraphExec_t* exec);
+// head of a run: the stop row the head's last sweep writes starts from zero and, for min_iter = 0, row 0 comes from the mirror
+// (glx_sweep_put_err0 fills it before the head is launched or replayed).  Capturable.
+void glx_sweep_put_err0(SweepCore* c, const double* err0);
+int glx_sweep_head_rows(SweepCore* c);
+// the conditional sweeps behind the head, for the groups `c->walk` was started with (launch(t) enqueues sweep t), and the end of the
+// run: ev1, synchronise, device time since ev0.  See sweep_core.hip.
+int glx_sweep_tail(SweepCore* c, const std::function<int(int)>& launch, float* device_ms_out);
+int glx_sweep_stop_values_core(const SweepCore* c, int b, int64_t cap, double* vals, int* first, int* count);
+// where the (n, C) iterate goes for the label decision: fp64 straight into the projector's scores, float32 through `dense`
+int glx_sweep_project_target(SweepCore* c, void** prob);
 

@@ -1,7 +1,9 @@
 // Iteration drivers on top of the sliced-ELL SpMM: the Poisson sweep with its fused stop
 // column (reference graphlearning/ssl.py:631-670), the PoissonMBO heat loop (ssl.py:826-827)
 // and the one-shot glx_spmm_bias.  All iterations run on the device; the host only reads
-// back the per-iteration stop-test maxima in small chunks.
+// back the per-iteration stop-test maxima in small chunks.  The buffers of a prepared sweep and the loop of the stop test
+// are sweep_core.hip's, shared with the stacked trials (groups.hip); this file adds the single form's head (eager first run,
+// then one captured graph), its dense and row-wise problem uploads, and the heat loop.
 #include "glx_internal.h"
 #include <string.h>
 #include <map>
@@ -10,46 +12,24 @@
 #include <algorithm>
 
 static const int ERR_SHARDS = 64;
-static const int TAIL_CHUNK = 16;
 
-struct glx_sweep {
-  glx_graph* P = nullptr;
-  int device = 0;   // copied from P: destruction must not touch the operator (it may already be gone)
-  int C = 0, min_iter = 0, max_iter = 0;
-  bool has_w = false, use_graph = false;
-  RecLayout L;
-  SellPlan* plan = nullptr;
-  int64_t n_rows = 0, n_cols = 0;
-  void* buf[2] = {nullptr, nullptr};
-  void* bias = nullptr;
-  uint8_t* slot_has_bias = nullptr;
-  bool bias_set = false;
-  double *deg = nullptr, *vinf = nullptr, *w0 = nullptr;
-  unsigned long long* err = nullptr;        // [(max_iter+1) * ERR_SHARDS]
-  unsigned long long* h_err = nullptr;      // pinned mirror
-  void* dense = nullptr;                    // staging (n_cols, C)
-  glx_work* work = nullptr;                // stream + events of this sweep, from the per-device list of idle sets
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  glx_projector* proj = nullptr;            // label decision on the device-resident state (glx_sweep_project)
+struct glx_sweep : SweepCore {
+  bool use_graph = false;
   hipGraphExec_t head_exec = nullptr;       // captured: reset + min_iter unconditional sweeps
   int64_t runs = 0;                         // glx_sweep_run calls so far (the first one launches eagerly)
   std::map<long, hipGraphExec_t> iter_exec; // heat loop graphs keyed by (iters, parity)
-  int cur = 0;
-  int64_t launches = 0;
-  double err0 = 0.0, thresh = 0.0;
-  int tested_first = 0, tested_count = 0;   // stop values err[t], t = tested_first .. +tested_count-1, of the last glx_sweep_run (in h_err)
-  // sparse right-hand side (glx_sweep_set_problem_rows): record indices of the rows set by the previous call
+  double err0 = 0.0;
+  // sparse right-hand side (glx_sweep_set_problem_rows): the rows set by the previous call.  Pooled blocks like the core's.
   int32_t* row_slot = nullptr;              // [n_rows] record index -> its (first) slot in the plan
-  int32_t* prev_rec = nullptr;              // [prev_cap] records whose bias / flag / w0 the previous problem set
-  int64_t* prev_row = nullptr;              // [prev_cap] the same rows in the caller's numbering (for w0)
-  int64_t prev_m = 0, prev_cap = 0;
-  void* rows_stage = nullptr;               // device staging for (rows, Db_rows, w0_rows)
-  size_t rows_stage_cap = 0;
+  void* prev = nullptr;                     // [cap] rows in the caller's numbering (for w0), then [cap] their record indices
+  size_t prev_bytes = 0;                    // cap = prev_bytes / 12
+  int64_t prev_m = 0;
   bool vectors_set = false;
+  int64_t* prev_row() const { return (int64_t*)prev; }
+  int32_t* prev_rec() const { return (int32_t*)(prev_row() + prev_bytes / 12); }
 };
 
-static size_t rec_bytes(const glx_sweep* s, int64_t rows) { return (size_t)rows * s->L.ld * s->L.esize; }
+static size_t rec_bytes(const glx_sweep* s, int64_t rows) { return (size_t)rows * s->rec_bytes(); }
 
 extern "C" int glx_sweep_destroy(glx_sweep* s) {
   if (!s) return GLX_OK;
@@ -57,22 +37,9 @@ extern "C" int glx_sweep_destroy(glx_sweep* s) {
   if (s->stream) hipStreamSynchronize(s->stream);
   if (s->head_exec) hipGraphExecDestroy(s->head_exec);
   for (auto& kv : s->iter_exec) hipGraphExecDestroy(kv.second);
-  glx_pool_free(s->buf[0]);
-  glx_pool_free(s->buf[1]);
-  glx_pool_free(s->bias);
-  glx_pool_free(s->slot_has_bias);
-  glx_pool_free(s->deg);
-  glx_pool_free(s->vinf);
-  glx_pool_free(s->w0);
-  glx_pool_free(s->err);
-  glx_pinned_free(s->h_err);        // (the stream was synchronised at the top)
-  glx_pool_free(s->dense);
-  hipFree(s->row_slot);
-  hipFree(s->prev_rec);
-  hipFree(s->prev_row);
-  hipFree(s->rows_stage);
-  glx_projector_destroy(s->proj);
-  glx_work_release(s->work);      // (the stream was synchronised at the top)
+  glx_pool_free(s->row_slot);
+  glx_pool_free(s->prev);
+  glx_sweep_core_destroy(s);
   delete s;
   return GLX_OK;
 }
@@ -82,65 +49,14 @@ extern "C" int glx_sweep_create(glx_graph* P, int C, int min_iter, int max_iter,
   *out = nullptr;
   GLX_CHECK(min_iter >= 0 && max_iter >= 0, GLX_EINVAL, "glx_sweep_create: negative iteration bound");
   GLX_HIP(hipSetDevice(P->device));
+  RecLayout L;
+  GLX_UP(glx_make_layout(C, P->dtype, max_iter > 0, &L));
   glx_sweep* s = new glx_sweep();
-  s->P = P;
-  s->device = P->device;
-  s->C = C;
-  s->min_iter = min_iter;
-  s->max_iter = max_iter;
-  s->has_w = max_iter > 0;
   s->use_graph = use_hipgraph != 0;
-  s->n_rows = P->n_rows;
-  s->n_cols = P->n_cols;
-  int rc = glx_make_layout(C, P->dtype, s->has_w, &s->L);
-  if (rc) { delete s; return rc; }
-  rc = glx_graph_plan(P, s->L.G, &s->plan);
-  if (rc) { delete s; return rc; }
-// (work buffers from the size-class pool of memory.hip: a dozen hipMalloc / hipFree pairs per sweep object cost milliseconds)
-#define SW_POOL(call) do { int rc_ = (call); if (rc_) { glx_sweep_destroy(s); return rc_; } } while (0)
-#define SW_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { glx_set_error("%s -> %s", #call, hipGetErrorString(e_)); glx_sweep_destroy(s); return GLX_EHIP; } } while (0)
-  rc = glx_work_acquire(P->device, &s->work);
+  int rc = glx_sweep_core_create(s, P, L, C, 1, ERR_SHARDS, min_iter, max_iter, max_iter > 0);
   if (rc) { glx_sweep_destroy(s); return rc; }
-  s->stream = s->work->stream;
-  s->ev0 = s->work->ev[0];
-  s->ev1 = s->work->ev[1];
-  const size_t rb = std::max<size_t>(rec_bytes(s, s->n_cols), 64);
-  SW_POOL(glx_pool_alloc((void**)&s->buf[0], rb));
-  SW_POOL(glx_pool_alloc((void**)&s->buf[1], rb));
-  // (on the sweep's own stream: it is non-blocking, so a null-stream memset -- asynchronous to the host --
-  // would not be ordered against the first pack / upload and could land after it)
-  SW_HIP(hipMemsetAsync(s->buf[0], 0, rb, s->stream));
-  SW_HIP(hipMemsetAsync(s->buf[1], 0, rb, s->stream));
-  SW_POOL(glx_pool_alloc((void**)&s->bias, std::max<size_t>(rec_bytes(s, s->n_rows), 64)));
-  SW_HIP(hipMemsetAsync(s->bias, 0, std::max<size_t>(rec_bytes(s, s->n_rows), 64), s->stream));
-  SW_POOL(glx_pool_alloc((void**)&s->slot_has_bias, std::max<size_t>((size_t)s->plan->nslices * s->plan->R, 64)));
-  SW_POOL(glx_pool_alloc((void**)&s->dense, std::max<size_t>((size_t)s->n_cols * C * s->L.esize, 64)));
-  if (s->has_w) {
-    SW_POOL(glx_pool_alloc((void**)&s->deg, std::max<size_t>(s->n_rows * 8, 64)));
-    SW_POOL(glx_pool_alloc((void**)&s->vinf, std::max<size_t>(s->n_rows * 8, 64)));
-    SW_POOL(glx_pool_alloc((void**)&s->w0, std::max<size_t>(s->n_cols * 8, 64)));
-    const size_t eb = (size_t)(max_iter + 1) * ERR_SHARDS * 8;
-    SW_POOL(glx_pool_alloc((void**)&s->err, eb));
-    SW_POOL(glx_pinned_alloc((void**)&s->h_err, eb));
-  }
-#undef SW_HIP
   *out = s;
   return GLX_OK;
-}
-
-// per-slot flag: does the row's bias record hold any nonzero?  (Poisson's Db = D^-1 b is
-// nonzero on the m labelled rows only, ssl.py:620-622,636: the sweep then skips reading it.)
-__global__ void bias_flags_kernel(const int32_t* __restrict__ slot_row, uint8_t* __restrict__ flags, int64_t nslots,
-                                  const char* __restrict__ bias, int rec_bytes) {
-  const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (slot >= nslots) return;
-  const int row = slot_row[slot];
-  uint8_t f = 0;
-  if (row >= 0) {
-    const unsigned long long* r = (const unsigned long long*)(bias + (size_t)row * rec_bytes);
-    for (int i = 0; i < rec_bytes / 8; ++i) f |= (r[i] << 1) != 0;   // -0.0 counts as zero
-  }
-  flags[slot] = f;
 }
 
 // captured launch sequences bake in whether a bias is read: drop them when that changes
@@ -151,25 +67,19 @@ static void drop_graphs_if_bias_changes(glx_sweep* s, bool will_have_bias) {
   s->iter_exec.clear();
 }
 
-static int upload_bias(glx_sweep* s, const void* Db) {
-  const int64_t nslots = s->plan->nslices * s->plan->R;
-  drop_graphs_if_bias_changes(s, Db != nullptr);
-  if (!Db) {
-    GLX_HIP(hipMemsetAsync(s->bias, 0, rec_bytes(s, s->n_rows), s->stream));
-    GLX_HIP(hipMemsetAsync(s->slot_has_bias, 0, std::max<int64_t>(nslots, 1), s->stream));
-    s->bias_set = false;
-    return GLX_OK;
-  }
-  GLX_UP(glx_upload(s->dense, Db, (size_t)s->n_rows * s->C * s->L.esize, s->stream, __func__));
-  int rc = glx_pack_records(s->dense, s->bias, s->n_rows, s->L, s->P->dtype, nullptr, s->stream, s->P->d_perm);
-  if (rc) return rc;
-  if (nslots > 0) {
-    hipLaunchKernelGGL(bias_flags_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s->stream,
-                       s->plan->d_slot_row, s->slot_has_bias, nslots, (const char*)s->bias, s->L.ld * s->L.esize);
-    GLX_HIP(hipGetLastError());
-  }
-  s->bias_set = true;
+static int zero_bias(glx_sweep* s) {
+  GLX_HIP(hipMemsetAsync(s->bias, 0, rec_bytes(s, s->n_rows), s->stream));
+  GLX_HIP(hipMemsetAsync(s->slot_has_bias, 0, std::max<int64_t>(s->nslots(), 1), s->stream));
   return GLX_OK;
+}
+
+static int upload_bias(glx_sweep* s, const void* Db) {
+  drop_graphs_if_bias_changes(s, Db != nullptr);
+  s->bias_set = Db != nullptr;
+  if (!Db) return zero_bias(s);
+  GLX_UP(glx_upload(s->dense, Db, (size_t)s->n_rows * s->C * s->L.esize, s->stream, __func__));
+  GLX_UP(glx_pack_records(s->dense, s->bias, s->n_rows, s->L, s->P->dtype, nullptr, s->stream, s->P->d_perm));
+  return glx_bias_flags_async(s->plan, s->bias, (int)s->rec_bytes(), s->slot_has_bias, s->stream);
 }
 
 extern "C" int glx_sweep_set_problem(glx_sweep* s, const void* Db, const double* w0, const double* deg, const double* vinf) {
@@ -178,9 +88,13 @@ extern "C" int glx_sweep_set_problem(glx_sweep* s, const void* Db, const double*
   GLX_CHECK(w0 && deg && vinf, GLX_EINVAL, "glx_sweep_set_problem: null vector");
   GLX_CHECK(s->n_rows == s->n_cols, GLX_EINVAL, "glx_sweep_set_problem: operator must be square");
   GLX_HIP(hipSetDevice(s->P->device));
-  int rc = upload_bias(s, Db);
-  if (rc) return rc;
-  if (s->row_slot) { hipFree(s->row_slot); s->row_slot = nullptr; s->prev_m = 0; }   // a later sparse problem starts from scratch
+  if (s->row_slot) {   // a later sparse problem starts from scratch
+    GLX_HIP(hipStreamSynchronize(s->stream));   // (nothing in flight may still read a block the pool hands on)
+    glx_pool_free(s->row_slot);
+    s->row_slot = nullptr;
+    s->prev_m = 0;
+  }
+  GLX_UP(upload_bias(s, Db));
   s->vectors_set = true;
   GLX_UP(glx_upload(s->w0, w0, s->n_cols * 8, s->stream, __func__));   // caller order; packed through perm
   std::vector<double> degp, vinfp;
@@ -198,7 +112,6 @@ extern "C" int glx_sweep_set_problem(glx_sweep* s, const void* Db, const double*
     if (e != e) break;   // np.max keeps the NaN
   }
   s->err0 = e0;
-  s->thresh = 1.0 / (double)s->n_rows;   // `> 1/n`, ssl.py:667
   GLX_HIP(hipStreamSynchronize(s->stream));
   return GLX_OK;
 }
@@ -207,34 +120,12 @@ extern "C" int glx_sweep_set_problem(glx_sweep* s, const void* Db, const double*
 // Poisson's right-hand side Db = D^-1 b and the initial stop vector v0 are nonzero on the m labelled rows only
 // (ssl.py:620-622, 639-641): a new training set on a resident graph then costs a few KB of upload instead of a
 // dense (n, C) array, and the graph's own vectors (deg, vinf) are uploaded once.
-__global__ void permute_f64_kernel(const double* __restrict__ src, double* __restrict__ dst, const int32_t* __restrict__ perm, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[perm ? perm[i] : i];
-}
-
 extern "C" int glx_sweep_set_vectors(glx_sweep* s, const double* deg, const double* vinf) {
   GLX_CHECK(s && deg && vinf, GLX_EINVAL, "glx_sweep_set_vectors: null argument");
   GLX_CHECK(s->has_w, GLX_EINVAL, "glx_sweep_set_vectors: sweep was created without a stop column (max_iter = 0)");
   GLX_CHECK(s->n_rows == s->n_cols, GLX_EINVAL, "glx_sweep_set_vectors: operator must be square");
   GLX_HIP(hipSetDevice(s->device));
-  double* tmp = (double*)s->dense;   // staging (n, C) of the state dtype: C*esize >= 4 bytes per row is not enough for 2 x fp64
-  void* own = nullptr;
-  if ((size_t)s->C * s->L.esize < 16) { GLX_HIP(hipMalloc(&own, (size_t)s->n_rows * 16)); tmp = (double*)own; }
-  const unsigned grid = (unsigned)((s->n_rows + 255) / 256);
-  int rcu = glx_upload(tmp, deg, s->n_rows * 8, s->stream, __func__);
-  if (!rcu) rcu = glx_upload(tmp + s->n_rows, vinf, s->n_rows * 8, s->stream, __func__);
-  if (rcu) { hipFree(own); return rcu; }
-  hipError_t e = hipSuccess;
-  if (s->n_rows > 0) {
-    hipLaunchKernelGGL(permute_f64_kernel, dim3(grid), dim3(256), 0, s->stream, (const double*)tmp, s->deg, (const int32_t*)s->P->d_perm, s->n_rows);
-    hipLaunchKernelGGL(permute_f64_kernel, dim3(grid), dim3(256), 0, s->stream, (const double*)(tmp + s->n_rows), s->vinf,
-                       (const int32_t*)s->P->d_perm, s->n_rows);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  hipFree(own);
-  GLX_HIP(e);
-  s->thresh = 1.0 / (double)s->n_rows;   // `> 1/n`, ssl.py:667
+  GLX_UP(glx_sweep_set_vectors_core(s, deg, vinf));
   s->vectors_set = true;
   return GLX_OK;
 }
@@ -276,7 +167,7 @@ __global__ void set_rows_kernel(char* __restrict__ bias, int rec_bytes, uint8_t*
   const int32_t rec = inv ? inv[row] : (int32_t)row;
   const T v = Db_rows[i];
   ((T*)(bias + (size_t)rec * rec_bytes))[c] = v;
-  // flag: any nonzero in the record (-0.0 counts as zero, like bias_flags_kernel); benign race: every writer stores 1
+  // flag: any nonzero in the record (-0.0 counts as zero, like glx_bias_flags_kernel); benign race: every writer stores 1
   bool nz;
   if constexpr (sizeof(T) == 8) nz = ((unsigned long long)__double_as_longlong((double)v) << 1) != 0;
   else nz = ((unsigned)__float_as_int((float)v) << 1) != 0;
@@ -297,67 +188,48 @@ extern "C" int glx_sweep_set_problem_rows(glx_sweep* s, int64_t m, const int64_t
   for (int64_t q = 0; q < m; ++q)
     GLX_CHECK(rows[q] >= 0 && rows[q] < s->n_rows, GLX_EINVAL, "glx_sweep_set_problem_rows: row %lld out of range", (long long)rows[q]);
   GLX_HIP(hipSetDevice(s->device));
-  const int64_t nslots = s->plan->nslices * s->plan->R;
-  const int rb = s->L.ld * s->L.esize;
+  const int64_t nslots = s->nslots();
+  const int rb = (int)s->rec_bytes();
+  const bool f32 = s->P->dtype == GLX_F32;
   if (!s->row_slot) {
-    GLX_HIP(hipMalloc(&s->row_slot, std::max<size_t>((size_t)s->n_rows * 4, 64)));
+    GLX_UP(glx_pool_alloc((void**)&s->row_slot, std::max<size_t>((size_t)s->n_rows * 4, 64)));
     if (nslots > 0) {
       hipLaunchKernelGGL(row_slot_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s->stream, (const int32_t*)s->plan->d_slot_row,
                          s->row_slot, nslots);
       GLX_HIP(hipGetLastError());
     }
     // from a dense problem to sparse ones: start from an all-zero bias
-    GLX_HIP(hipMemsetAsync(s->bias, 0, rec_bytes(s, s->n_rows), s->stream));
-    GLX_HIP(hipMemsetAsync(s->slot_has_bias, 0, std::max<int64_t>(nslots, 1), s->stream));
+    GLX_UP(zero_bias(s));
     GLX_HIP(hipMemsetAsync(s->w0, 0, std::max<size_t>(s->n_cols * 8, 8), s->stream));
     s->prev_m = 0;
   }
   drop_graphs_if_bias_changes(s, true);
   if (s->prev_m > 0) {
-    const int64_t tot = s->prev_m * s->L.ld;
-    if (s->P->dtype == GLX_F32)
-      hipLaunchKernelGGL(clear_rows_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, (char*)s->bias, rb, s->slot_has_bias,
-                         (const int32_t*)s->row_slot, s->w0, (const int32_t*)s->prev_rec, (const int64_t*)s->prev_row, s->prev_m, s->L.ld);
-    else
-      hipLaunchKernelGGL(clear_rows_kernel<double>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, (char*)s->bias, rb, s->slot_has_bias,
-                         (const int32_t*)s->row_slot, s->w0, (const int32_t*)s->prev_rec, (const int64_t*)s->prev_row, s->prev_m, s->L.ld);
+    const dim3 grid((unsigned)((s->prev_m * s->L.ld + 255) / 256));
+    auto* clear = f32 ? clear_rows_kernel<float> : clear_rows_kernel<double>;
+    hipLaunchKernelGGL(clear, grid, dim3(256), 0, s->stream, (char*)s->bias, rb, s->slot_has_bias, (const int32_t*)s->row_slot, s->w0,
+                       (const int32_t*)s->prev_rec(), (const int64_t*)s->prev_row(), s->prev_m, s->L.ld);
     GLX_HIP(hipGetLastError());
     s->prev_m = 0;
   }
   if (m > 0) {
-    if (s->prev_cap < m) {
-      hipFree(s->prev_rec);
-      hipFree(s->prev_row);
-      s->prev_rec = nullptr;
-      s->prev_row = nullptr;
-      s->prev_cap = 0;
-      const int64_t cap = std::max<int64_t>(m * 2, 256);
-      GLX_HIP(hipMalloc(&s->prev_rec, cap * 4));
-      GLX_HIP(hipMalloc(&s->prev_row, cap * 8));
-      s->prev_cap = cap;
-    }
+    GLX_UP(glx_sweep_reserve(s, &s->prev, &s->prev_bytes, (size_t)m * 12));   // (the clear above may still be reading the old block)
     const size_t es = s->L.esize;
     const size_t b_rows = (size_t)m * 8, b_db = ((size_t)m * s->C * es + 7) / 8 * 8, b_w = (size_t)m * 8;
-    if (s->rows_stage_cap < b_rows + b_db + b_w) {
-      hipFree(s->rows_stage);
-      s->rows_stage = nullptr;
-      s->rows_stage_cap = 0;
-      GLX_HIP(hipMalloc(&s->rows_stage, 2 * (b_rows + b_db + b_w)));
-      s->rows_stage_cap = 2 * (b_rows + b_db + b_w);
-    }
-    char* st = (char*)s->rows_stage;
+    GLX_UP(glx_sweep_reserve(s, &s->stage, &s->stage_cap, b_rows + b_db + b_w));
+    char* st = (char*)s->stage;
     GLX_UP(glx_upload(st, rows, b_rows, s->stream, __func__));
     GLX_UP(glx_upload(st + b_rows, Db_rows, (size_t)m * s->C * es, s->stream, __func__));
     GLX_UP(glx_upload(st + b_rows + b_db, w0_rows, b_w, s->stream, __func__));
-    const int64_t tot = m * s->C;
-    if (s->P->dtype == GLX_F32)
-      hipLaunchKernelGGL(set_rows_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, (char*)s->bias, rb, s->slot_has_bias,
-                         (const int32_t*)s->row_slot, s->w0, (const int64_t*)st, (const int32_t*)s->P->d_inv, (const float*)(st + b_rows),
-                         (const double*)(st + b_rows + b_db), m, s->C, s->prev_rec, s->prev_row);
+    const dim3 grid((unsigned)((m * s->C + 255) / 256));
+    if (f32)
+      hipLaunchKernelGGL(set_rows_kernel<float>, grid, dim3(256), 0, s->stream, (char*)s->bias, rb, s->slot_has_bias, (const int32_t*)s->row_slot,
+                         s->w0, (const int64_t*)st, (const int32_t*)s->P->d_inv, (const float*)(st + b_rows), (const double*)(st + b_rows + b_db), m,
+                         s->C, s->prev_rec(), s->prev_row());
     else
-      hipLaunchKernelGGL(set_rows_kernel<double>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, (char*)s->bias, rb, s->slot_has_bias,
-                         (const int32_t*)s->row_slot, s->w0, (const int64_t*)st, (const int32_t*)s->P->d_inv, (const double*)(st + b_rows),
-                         (const double*)(st + b_rows + b_db), m, s->C, s->prev_rec, s->prev_row);
+      hipLaunchKernelGGL(set_rows_kernel<double>, grid, dim3(256), 0, s->stream, (char*)s->bias, rb, s->slot_has_bias, (const int32_t*)s->row_slot,
+                         s->w0, (const int64_t*)st, (const int32_t*)s->P->d_inv, (const double*)(st + b_rows), (const double*)(st + b_rows + b_db), m,
+                         s->C, s->prev_rec(), s->prev_row());
     GLX_HIP(hipGetLastError());
     s->prev_m = m;
   }
@@ -369,66 +241,22 @@ extern "C" int glx_sweep_set_problem_rows(glx_sweep* s, int64_t m, const int64_t
 
 static int enqueue_iterate(glx_sweep* s, int iters);
 
-static int launch_sweep(glx_sweep* s, int t, bool with_stop) {
-  SweepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.plan = s->plan;
-  a.L = s->L;
-  a.dtype = s->P->dtype;
-  a.xin = s->buf[s->cur];
-  a.xout = s->buf[s->cur ^ 1];
-  a.bias = s->bias_set ? s->bias : nullptr;
-  a.slot_has_bias = s->bias_set ? s->slot_has_bias : nullptr;
-  a.has_w = s->has_w;
-  a.n_rows = s->n_rows;
-  if (with_stop) {
-    a.deg = s->deg;
-    a.vinf = s->vinf;
-    a.thresh = s->thresh;
-    a.err_prev = t >= s->min_iter ? s->err + (size_t)t * ERR_SHARDS : nullptr;
-    a.err_next = t + 1 >= s->min_iter ? s->err + (size_t)(t + 1) * ERR_SHARDS : nullptr;
-  }
-  int rc = glx_launch_spmm(a, s->stream);
-  if (rc) return rc;
-  s->cur ^= 1;
-  s->launches++;
-  return GLX_OK;
-}
-
 // reset state + the min_iter unconditional sweeps; identical every run -> capturable
 static int enqueue_head(glx_sweep* s) {
-  // the stop values the head's sweeps write: rows min_iter (written by sweep min_iter - 1) and, for min_iter = 0, row 0; the rows of a
-  // tail chunk are cleared in front of that chunk (glx_sweep_run) -- not all max_iter + 1 rows on every run (512 KB, 6.6 us of a
-  // 620 us step at config 2)
-  {
-    const int head_rows = std::min(s->min_iter, s->max_iter);
-    // (a kernel, not a memset node: this sequence is captured and replayed -- glx_zero_async, glx_internal.h)
-    { int rz = glx_zero_async(s->err + (size_t)head_rows * ERR_SHARDS, (size_t)ERR_SHARDS * 8, s->stream); if (rz) return rz; }
-  }
-  if (s->min_iter == 0) {
-    union { double d; unsigned long long u; } cv;
-    cv.d = s->err0;
-    s->h_err[0] = cv.u;
-    GLX_HIP(hipMemcpyAsync(s->err, s->h_err, 8, hipMemcpyHostToDevice, s->stream));
-  }
+  GLX_UP(glx_sweep_head_rows(s));
   s->cur = 0;
-  int rc = glx_pack_records(nullptr, s->buf[0], s->n_cols, s->L, s->P->dtype, s->w0, s->stream, s->P->d_perm);   // u = 0 (ssl.py:645), w = w0
-  if (rc) return rc;
-  const int head = std::min(s->min_iter, s->max_iter);
-  for (int t = 0; t < head; ++t) {
-    rc = launch_sweep(s, t, true);
-    if (rc) return rc;
-  }
+  GLX_UP(glx_pack_records(nullptr, s->buf[0], s->n_cols, s->L, s->P->dtype, s->w0, s->stream, s->P->d_perm));   // u = 0 (ssl.py:645), w = w0
+  for (int t = 0; t < s->walk.head; ++t) GLX_UP(glx_sweep_launch(s, t, true, 0));
   return GLX_OK;
 }
 
 extern "C" int glx_sweep_run(glx_sweep* s, int* T_out, float* device_ms_out) {
   GLX_CHECK(s && s->has_w, GLX_EINVAL, "glx_sweep_run: sweep has no stop column");
   GLX_HIP(hipSetDevice(s->P->device));
-  const int head = std::min(s->min_iter, s->max_iter);
-  int rc;
   const int64_t launches0 = s->launches;
+  s->walk.start(1, 1, s->min_iter, s->max_iter, s->thresh);
   GLX_HIP(hipEventRecord(s->ev0, s->stream));
+  glx_sweep_put_err0(s, &s->err0);
   // A model that is fitted once never earns its launch graph back: capture + instantiate + the first launch of a fresh executable graph +
   // its destruction cost 1.1-1.4 ms against 0.35 ms of launching the same 50 sweeps one by one (they run behind each other either way:
   // 0.62 ms of device time; profiles/r06_fresh_path.txt).  The first run of a sweep object therefore launches eagerly; the graph is captured
@@ -436,101 +264,22 @@ extern "C" int glx_sweep_run(glx_sweep* s, int* T_out, float* device_ms_out) {
   const bool replay = s->use_graph && (s->runs > 0 || s->head_exec);
   ++s->runs;
   if (replay) {
-    if (!s->head_exec) {
-      hipGraph_t graph;
-      GLX_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-      rc = enqueue_head(s);
-      hipError_t e = hipStreamEndCapture(s->stream, &graph);
-      if (rc) return rc;
-      GLX_HIP(e);
-      GLX_HIP(hipGraphInstantiate(&s->head_exec, graph, nullptr, nullptr, 0));
-      GLX_HIP(hipGraphDestroy(graph));
-    } else {
-      s->launches += head;
-    }
-    if (s->min_iter == 0) {
-      union { double d; unsigned long long u; } cv;
-      cv.d = s->err0;
-      s->h_err[0] = cv.u;
-    }
+    if (!s->head_exec) GLX_UP(glx_sweep_capture(s, [&]() { return enqueue_head(s); }, &s->head_exec));
     GLX_HIP(hipGraphLaunch(s->head_exec, s->stream));
-    s->cur = head & 1;
+    s->cur = s->walk.head & 1;
   } else {
-    rc = enqueue_head(s);
-    if (rc) return rc;
+    GLX_UP(enqueue_head(s));
   }
-  // tail: conditional sweeps in chunks; each kernel exits at once when the stop test
-  // (read from the previous kernel's maxima) already holds, so over-launching is harmless.
-  int T = head;
-  int t = head;
-  bool stopped = false;
-  while (!stopped && t < s->max_iter) {
-    // check err[t] first
-    GLX_HIP(hipMemcpyAsync(s->h_err + (size_t)t * ERR_SHARDS, s->err + (size_t)t * ERR_SHARDS, ERR_SHARDS * 8, hipMemcpyDeviceToHost, s->stream));
-    GLX_HIP(hipStreamSynchronize(s->stream));
-    {
-      unsigned long long m = 0;
-      for (int k = 0; k < ERR_SHARDS; ++k) m = std::max(m, s->h_err[(size_t)t * ERR_SHARDS + k]);
-      union { double d; unsigned long long u; } cv;
-      cv.u = m;
-      if (!(cv.d > s->thresh)) { stopped = true; T = t; break; }   // NaN stops the loop, like `nan > 1/n` (ssl.py:667)
-    }
-    const int end = std::min(s->max_iter, t + TAIL_CHUNK);
-    const int t0 = t;
-    const int cur0 = s->cur;
-    // rows t0 + 1 .. end: what this chunk's sweeps write (atomic maxima: they must start from 0)
-    GLX_HIP(hipMemsetAsync(s->err + (size_t)(t0 + 1) * ERR_SHARDS, 0, (size_t)(end - t0) * ERR_SHARDS * 8, s->stream));
-    for (; t < end; ++t) {
-      rc = launch_sweep(s, t, true);
-      if (rc) return rc;
-    }
-    // which of the chunk's sweeps really ran?
-    GLX_HIP(hipMemcpyAsync(s->h_err + (size_t)(t0 + 1) * ERR_SHARDS, s->err + (size_t)(t0 + 1) * ERR_SHARDS,
-                           (size_t)(end - t0) * ERR_SHARDS * 8, hipMemcpyDeviceToHost, s->stream));
-    GLX_HIP(hipStreamSynchronize(s->stream));
-    T = end;
-    for (int q = t0 + 1; q < end; ++q) {   // sweep q ran iff err[q] > thresh
-      unsigned long long m = 0;
-      for (int k = 0; k < ERR_SHARDS; ++k) m = std::max(m, s->h_err[(size_t)q * ERR_SHARDS + k]);
-      union { double d; unsigned long long u; } cv;
-      cv.u = m;
-      if (!(cv.d > s->thresh)) { T = q; stopped = true; break; }
-    }
-    if (stopped) s->cur = cur0 ^ ((T - t0) & 1);
-    t = stopped ? T : end;
-  }
-  if (!stopped) T = t;
-  GLX_HIP(hipEventRecord(s->ev1, s->stream));
-  GLX_HIP(hipStreamSynchronize(s->stream));
-  if (device_ms_out) GLX_HIP(hipEventElapsedTime(device_ms_out, s->ev0, s->ev1));
-  if (T_out) *T_out = T;
+  GLX_UP(glx_sweep_tail(s, [&](int t) { return glx_sweep_launch(s, t, true, 0); }, device_ms_out));
+  if (T_out) *T_out = s->walk.T[0];
   // count the sweeps that really ran: kernels of a tail chunk launched past the stop test exit at once
-  s->launches = launches0 + T;
-  s->tested_first = head;
-  s->tested_count = T - head + (stopped ? 1 : 0);   // err[head..T]; the value at T = max_iter is never compared (ssl.py:667)
+  s->launches = launches0 + s->walk.T[0];
   return GLX_OK;
 }
 
-// The stop values the last glx_sweep_run compared with 1/n: vals[i] = max|v_t - v_inf| at t = *first + i, the last one
-// being the value at t = T.  They are computed as deg*(P w) (the fused column), not as the reference's separate
-// product RW*v (ssl.py:669): equal up to rounding.  The caller (ssl.poisson) uses them to recognise the one case in
-// which the two roundings could decide differently -- a value within a few ulps of 1/n -- and settles that case with
-// the reference's own recurrence.
 extern "C" int glx_sweep_stop_values(const glx_sweep* s, int64_t cap, double* vals, int* first, int* count) {
   GLX_CHECK(s && first && count, GLX_EINVAL, "glx_sweep_stop_values: null argument");
-  *first = s->tested_first;
-  *count = s->tested_count;
-  if (!vals) return GLX_OK;
-  GLX_CHECK(cap >= s->tested_count, GLX_EINVAL, "glx_sweep_stop_values: %lld values, room for %lld", (long long)s->tested_count, (long long)cap);
-  for (int i = 0; i < s->tested_count; ++i) {
-    const size_t t = (size_t)(s->tested_first + i);
-    unsigned long long m = 0;
-    for (int k = 0; k < ERR_SHARDS; ++k) m = std::max(m, s->h_err[t * ERR_SHARDS + k]);
-    union { double d; unsigned long long u; } cv;
-    cv.u = m;
-    vals[i] = cv.d;
-  }
-  return GLX_OK;
+  return glx_sweep_stop_values_core(s, 0, cap, vals, first, count);
 }
 
 extern "C" int glx_sweep_fetch(glx_sweep* s, void* u_out) {
@@ -557,17 +306,9 @@ extern "C" int glx_sweep_project_iterate(glx_sweep* s, const double* priors, dou
             "glx_sweep_project: then_iterate needs to_onehot and a square operator");
   GLX_HIP(hipSetDevice(s->device));
   const int dtype = s->P->dtype;
-  // an fp64 state is unpacked straight into the projector's own (n, C) array; a float32 one goes through `dense` and is widened
-  void* prob = s->dense;
-  int rc;
-  if (dtype == GLX_F64) {
-    double* scores = nullptr;
-    rc = glx_project_scores(&s->proj, s->n_rows, s->C, s->stream, &scores);
-    if (rc) return rc;
-    prob = scores;
-  }
-  rc = glx_unpack_records(s->buf[s->cur], prob, s->n_rows, s->L, dtype, s->stream, s->P->d_perm);
-  if (rc) return rc;
+  void* prob = nullptr;
+  GLX_UP(glx_sweep_project_target(s, &prob));
+  GLX_UP(glx_unpack_records(s->buf[s->cur], prob, s->n_rows, s->L, dtype, s->stream, s->P->d_perm));
   const long long* d_labels = nullptr;
   // what goes with the decision (the labels, waited for) and what follows it (the one-hot state, the next sweeps: enqueued, not
   // awaited -- the next call on this sweep is ordered behind them in its stream)
@@ -611,17 +352,6 @@ extern "C" int glx_sweep_set_state(glx_sweep* s, const void* u0, const void* Db)
   return GLX_OK;
 }
 
-// rows of a bias given one by one (heat sweeps: no stop column, no flags per row needed beyond bias_flags_kernel's pass)
-template <typename T>
-__global__ void scatter_bias_rows_kernel(char* __restrict__ bias, int rec_bytes, const int64_t* __restrict__ rows, const int32_t* __restrict__ inv,
-                                         const T* __restrict__ Db_rows, int64_t m, int C) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m * C) return;
-  const int64_t row = rows[i / C];
-  const int32_t rec = inv ? inv[row] : (int32_t)row;
-  ((T*)(bias + (size_t)rec * rec_bytes))[i % C] = Db_rows[i];
-}
-
 extern "C" int glx_sweep_set_state_labels(glx_sweep* s, const int64_t* labels, int64_t m, const int64_t* rows, const void* Db_rows) {
   GLX_CHECK(s && labels, GLX_EINVAL, "glx_sweep_set_state_labels: null argument");
   GLX_CHECK(!s->has_w, GLX_EINVAL, "glx_sweep_set_state_labels: only for sweeps created with max_iter = 0");
@@ -630,41 +360,19 @@ extern "C" int glx_sweep_set_state_labels(glx_sweep* s, const int64_t* labels, i
   for (int64_t q = 0; q < m; ++q)
     GLX_CHECK(rows[q] >= 0 && rows[q] < s->n_rows, GLX_EINVAL, "glx_sweep_set_state_labels: row %lld out of range", (long long)rows[q]);
   GLX_HIP(hipSetDevice(s->P->device));
-  const int64_t nslots = s->plan->nslices * s->plan->R;
-  const int rb = s->L.ld * s->L.esize;
   const size_t es = s->L.esize;
   const size_t b_lab = (size_t)s->n_rows * 8, b_rows = (size_t)m * 8, b_db = ((size_t)m * s->C * es + 7) / 8 * 8;
-  if (s->rows_stage_cap < b_lab + b_rows + b_db) {
-    GLX_HIP(hipStreamSynchronize(s->stream));
-    hipFree(s->rows_stage);
-    s->rows_stage = nullptr;
-    s->rows_stage_cap = 0;
-    GLX_HIP(hipMalloc(&s->rows_stage, b_lab + 2 * (b_rows + b_db) + 64));
-    s->rows_stage_cap = b_lab + 2 * (b_rows + b_db) + 64;
-  }
-  char* st = (char*)s->rows_stage;
+  GLX_UP(glx_sweep_reserve(s, &s->stage, &s->stage_cap, b_lab + b_rows + b_db));
+  char* st = (char*)s->stage;
   drop_graphs_if_bias_changes(s, m > 0);
   GLX_UP(glx_upload(st, labels, b_lab, s->stream, __func__));
-  int rc = glx_onehot_records((const long long*)st, s->buf[0], s->P->dtype, s->n_rows, s->L, s->P->d_perm, s->stream);   // u = onehot(labels)
-  if (rc) return rc;
-  GLX_HIP(hipMemsetAsync(s->bias, 0, rec_bytes(s, s->n_rows), s->stream));
-  GLX_HIP(hipMemsetAsync(s->slot_has_bias, 0, std::max<int64_t>(nslots, 1), s->stream));
-  if (m > 0) {
+  GLX_UP(glx_onehot_records((const long long*)st, s->buf[0], s->P->dtype, s->n_rows, s->L, s->P->d_perm, s->stream));   // u = onehot(labels)
+  GLX_UP(zero_bias(s));
+  if (m > 0) {   // (heat sweeps: no stop column, and no flags per row beyond glx_bias_flags_kernel's pass)
     GLX_UP(glx_upload(st + b_lab, rows, b_rows, s->stream, __func__));
     GLX_UP(glx_upload(st + b_lab + b_rows, Db_rows, (size_t)m * s->C * es, s->stream, __func__));
-    const int64_t tot = m * s->C;
-    if (s->P->dtype == GLX_F32)
-      hipLaunchKernelGGL(scatter_bias_rows_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, (char*)s->bias, rb,
-                         (const int64_t*)(st + b_lab), (const int32_t*)s->P->d_inv, (const float*)(st + b_lab + b_rows), m, s->C);
-    else
-      hipLaunchKernelGGL(scatter_bias_rows_kernel<double>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, (char*)s->bias, rb,
-                         (const int64_t*)(st + b_lab), (const int32_t*)s->P->d_inv, (const double*)(st + b_lab + b_rows), m, s->C);
-    GLX_HIP(hipGetLastError());
-    if (nslots > 0) {
-      hipLaunchKernelGGL(bias_flags_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s->stream,
-                         s->plan->d_slot_row, s->slot_has_bias, nslots, (const char*)s->bias, rb);
-      GLX_HIP(hipGetLastError());
-    }
+    GLX_UP(glx_sweep_scatter_rows(s, (const int64_t*)(st + b_lab), st + b_lab + b_rows, nullptr, nullptr, m, 0));
+    GLX_UP(glx_bias_flags_async(s->plan, s->bias, (int)s->rec_bytes(), s->slot_has_bias, s->stream));
   }
   s->bias_set = m > 0;
   s->cur = 0;
@@ -673,36 +381,21 @@ extern "C" int glx_sweep_set_state_labels(glx_sweep* s, const int64_t* labels, i
 }
 
 static int enqueue_iterate(glx_sweep* s, int iters) {
-  int rc;
-  if (s->use_graph && iters > 1) {
-    const long key = (long)iters * 4 + s->cur * 2 + (s->bias_set ? 1 : 0);
-    auto it = s->iter_exec.find(key);
-    if (it == s->iter_exec.end()) {
-      hipGraph_t graph;
-      hipGraphExec_t exec;
-      const int cur0 = s->cur;
-      GLX_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-      rc = GLX_OK;
-      for (int t = 0; t < iters && rc == GLX_OK; ++t) rc = launch_sweep(s, t, false);
-      hipError_t e = hipStreamEndCapture(s->stream, &graph);
-      if (rc) return rc;
-      GLX_HIP(e);
-      GLX_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-      GLX_HIP(hipGraphDestroy(graph));
-      s->iter_exec[key] = exec;
-      s->cur = cur0;
-      s->launches -= iters;
-      it = s->iter_exec.find(key);
-    }
-    GLX_HIP(hipGraphLaunch(it->second, s->stream));
-    s->cur ^= (iters & 1);
-    s->launches += iters;
-  } else {
-    for (int t = 0; t < iters; ++t) {
-      rc = launch_sweep(s, t, false);
-      if (rc) return rc;
-    }
+  const auto sweeps = [&]() -> int {
+    for (int t = 0; t < iters; ++t) GLX_UP(glx_sweep_launch(s, t, false, 0));
+    return GLX_OK;
+  };
+  if (!s->use_graph || iters <= 1) return sweeps();
+  const long key = (long)iters * 4 + s->cur * 2 + (s->bias_set ? 1 : 0);
+  auto it = s->iter_exec.find(key);
+  if (it == s->iter_exec.end()) {
+    hipGraphExec_t exec;
+    GLX_UP(glx_sweep_capture(s, sweeps, &exec));
+    it = s->iter_exec.emplace(key, exec).first;
   }
+  GLX_HIP(hipGraphLaunch(it->second, s->stream));
+  s->cur ^= (iters & 1);
+  s->launches += iters;
   return GLX_OK;
 }
 
@@ -725,7 +418,7 @@ extern "C" int glx_spmm_bias(glx_graph* A, const void* Db, const void* u_in, voi
   if (rc) return rc;
   rc = glx_sweep_set_state(s, u_in, Db);
   if (!rc) {
-    for (int t = 0; t < iters && !rc; ++t) rc = launch_sweep(s, t, false);
+    for (int t = 0; t < iters && !rc; ++t) rc = glx_sweep_launch(s, t, false, 0);
     if (!rc && hipStreamSynchronize(s->stream) != hipSuccess) { glx_set_error("glx_spmm_bias: sync failed"); rc = GLX_EHIP; }
   }
   if (!rc) rc = glx_sweep_fetch(s, u_out);
@@ -778,7 +471,7 @@ extern "C" int glx_affine_iterate(glx_graph* A, const void* b, const void* u0, v
   while (!rc && err > tol && it < max_iter) {
     hipError_t e = hipMemsetAsync(d_err, 0, 8, s->stream);
     if (e == hipSuccess) {
-      rc = launch_sweep(s, (int)(it & 1), false);
+      rc = glx_sweep_launch(s, (int)(it & 1), false, 0);
       if (rc) break;
       if (A->dtype == GLX_F32)
         hipLaunchKernelGGL(absdiff_max_kernel<float>, dim3(grid), dim3(256), 0, s->stream, (const float*)s->buf[0], (const float*)s->buf[1], total, d_err);
@@ -865,12 +558,7 @@ extern "C" int glx_bias_flags_dev(glx_graph* P, int C, int has_w, const void* bi
   SellPlan* plan = nullptr;
   rc = glx_graph_plan(P, L.G, &plan);
   if (rc) return rc;
-  const int64_t nslots = plan->nslices * plan->R;
-  if (nslots == 0) return GLX_OK;
-  hipLaunchKernelGGL(bias_flags_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     plan->d_slot_row, flags, nslots, (const char*)bias_rec, L.ld * L.esize);
-  GLX_HIP(hipGetLastError());
-  return GLX_OK;
+  return glx_bias_flags_async(plan, bias_rec, L.ld * L.esize, flags, (hipStream_t)stream);
 }
 
 extern "C" int glx_sweep_step_dev(glx_graph* P, int C, int has_w, const void* xin, void* xout, const void* bias_rec,

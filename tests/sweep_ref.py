@@ -1,4 +1,5 @@
-"""Host restatement of the stop-column sweeps (glx_sweep_run, csrc/solver.hip; glx_sweep_groups_run, csrc/groups.hip) in plain
+"""Host restatement of the stop-column sweeps (glx_sweep_run, csrc/solver.hip; glx_sweep_groups_run, csrc/groups.hip; their shared
+loop glx_sweep_tail, csrc/sweep_core.hip) in plain
 numpy / scipy, and the fixtures tests/test_sweep_ref_host.py and tests/test_gpu_sweep_stop.py share.  No GPU, no library call.
 
 What the two entry points promise, and what `poisson_sweeps` states:

@@ -1,13 +1,15 @@
 """The stop-column forms of the sweep kernel (csrc/sweep.hip: HAS_W, what ssl.poisson(solver='gradient_descent') runs, and GRP, the
-stacked trials) and the host loops around them (glx_sweep_run, csrc/solver.hip; glx_sweep_groups_run, csrc/groups.hip), bit for bit
-against the host restatement tests/sweep_ref.py: the iterate u_T, the sweep count T, the first tested sweep and every stop value
+stacked trials) and the host loop around them (glx_sweep_tail, csrc/sweep_core.hip, on the walk of csrc/sweep_stop_plan.h; the heads
+are glx_sweep_run's, csrc/solver.hip, and glx_sweep_groups_run's, csrc/groups.hip), bit for bit against the host restatement
+tests/sweep_ref.py: the iterate u_T, the sweep count T, the first tested sweep and every stop value
 max|deg w - vinf| the run compared with 1 / n.  Everything is np.array_equal; equal_nan only where a NaN is the point.
 
 Fixture A (sweep_ref.ladder): 640 rows of lengths 0 .. 300 on both sides of every row class, positive weights, every row summing to
 0.5, so that the stop column halves per sweep and the scale of w0 places T: both parities inside a 16-sweep tail chunk, both sides of
 the chunk edge, the third chunk (the host's choice of ping-pong buffer).  Fixture B (sweep_ref.half_identity): P = I / 2, n = 1024,
 exact in both dtypes: the decision AT 1 / n; half_identity_rebound: a value equal to 1 / n in front of a larger one, where the kernel's
-own gate is what keeps u_T.  tests/test_sweep_ref_host.py holds the restatement and the fixtures' stop positions."""
+own gate is what keeps u_T.  tests/test_sweep_ref_host.py holds the restatement and the fixtures' stop positions;
+tests/test_sweep_stop_host.py the walk's chunked read-back, without a device."""
 import numpy as np
 import pytest
 import sweep_ref as R
@@ -140,6 +142,63 @@ def test_captured_head_and_sparse_problem(hip, ladder, C, dtype):
     sw.set_problem(R.bias(C, seed=41).astype(DT[dtype]), w0, deg, vinf)
     _same(_run(sw), by_rows, (C, dtype, 'dense'))
     sw.close()
+
+
+def _sparse_problems(C, dtype):
+    """Four training sets given by rows, in the order a resident sweep meets them: a subset of the rows (a row without entries among
+    them), one that keeps half of it and adds new rows, the empty one, the first again.  Each as (rows, Db_rows, w0_rows, err0, the
+    restatement's run on the dense arrays that are zero outside the rows)."""
+    A, deg, vinf, w_unit = R.fixture_a()
+    rng = np.random.default_rng(77)
+    first = np.concatenate([[0, 18], rng.choice(np.setdiff1d(np.arange(R.N), [0, 18]), size=78, replace=False)])
+    new = rng.choice(np.setdiff1d(np.arange(R.N), first), size=60, replace=False)
+    second = rng.permutation(np.concatenate([first[::2], new]))
+    problems = []
+    for rows, k, seed in ((first, R.K_T[4][0], 51), (second, R.K_T[6][0], 52), (first[:0], 0.0, 53), (first, R.K_T[4][0], 51)):
+        Db_rows = R.bias(C, seed=seed)[rows]
+        Db_rows[::5] = 0.0                          # labelled rows whose bias is zero: their flag stays down
+        w0_rows = 2.0 ** k * w_unit[rows]
+        Db, w0 = np.zeros((R.N, C)), np.zeros(R.N)
+        Db[rows], w0[rows] = Db_rows, w0_rows
+        want = R.poisson_sweeps(A, Db, w0, deg, vinf, R.MIN_ITER, R.MAX_ITER, DT[dtype])
+        problems.append((rows.astype(np.int64), Db_rows.astype(DT[dtype]), w0_rows, R.err0(deg, vinf, w0), want))
+    T = [p[4][1] for p in problems]
+    assert T[0] == T[3] and len(set(T[:3])) == 3 and sum(t > R.MIN_ITER for t in T[:3]) >= 2, T      # (holds on the CPU: no device involved)
+    assert problems[1][4][0].any() and not problems[2][4][0].any()
+    return problems
+
+
+@pytest.mark.parametrize('dtype', list(DT))
+def test_sparse_problems_in_turn(hip, ladder, dtype):
+    """The rows of a training set replace the previous set's rows -- bias, flags and start values of the rows that left are cleared, the
+    staging and the row lists grow -- in one prepared sweep (its head eager, then captured, then replayed) and in one group of a
+    stacked one, whose other groups do not move."""
+    A, deg, vinf, w_unit, graphs = ladder
+    dt, name = DT[dtype], np.dtype(DT[dtype]).name
+    G = graphs[dtype, 'renum']
+    sw = hip.Sweep(G, 12, min_iter=R.MIN_ITER, max_iter=R.MAX_ITER, use_hipgraph=True)
+    sw.set_vectors(deg, vinf)
+    for i, (rows, Db_rows, w0_rows, err0, want) in enumerate(_sparse_problems(12, dtype)):
+        sw.set_problem_rows(rows, Db_rows, w0_rows, err0)
+        _same(_run(sw), want, (dtype, 'single', i))
+    sw.close()
+    C, B, g = 3, 5, 2
+    groups = hip.SweepGroups(G, C, B, min_iter=R.MIN_ITER, max_iter=R.MAX_ITER)
+    groups.set_vectors(deg, vinf)
+    _set_groups(groups, C, B, dt, deg, vinf, w_unit)
+    others = None
+    for i, (rows, Db_rows, w0_rows, err0, want) in enumerate(_sparse_problems(C, dtype)):
+        groups.set_problem_rows(g, rows, Db_rows, w0_rows, err0)
+        T, _ = groups.run()
+        _same(_group(groups, T, g), want, (dtype, 'stacked', i))
+        got = [_group(groups, T, b) for b in range(B) if b != g]
+        if others is None:
+            others = got
+            for b, o in zip([b for b in range(B) if b != g], others):
+                _same(o, R.ladder_run(C, R.group_db_seed(b), R.group_k(b), R.MIN_ITER, R.MAX_ITER, name), (dtype, 'stacked', 'other', b))
+        for o, o0 in zip(got, others):
+            _same(o, o0, (dtype, 'stacked', i, 'others moved'))
+    groups.close()
 
 
 @pytest.mark.parametrize('dtype', list(DT))

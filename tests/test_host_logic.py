@@ -361,8 +361,10 @@ def test_captured_launch_sequences_hold_no_memset_node():
 
     captured = {
         'solver.hip: enqueue_head': body('solver.hip', 'static int enqueue_head(glx_sweep* s)', 'extern "C" int glx_sweep_run'),
-        'solver.hip: launch_sweep': body('solver.hip', 'static int launch_sweep(', 'static int enqueue_head('),
-        'groups.hip: grp_launch_sweep + grp_enqueue_head': body('groups.hip', 'static int grp_launch_sweep(', 'static double grp_err_value('),
+        'solver.hip: enqueue_iterate': body('solver.hip', 'static int enqueue_iterate(glx_sweep* s, int iters) {', 'extern "C" int glx_sweep_iterate('),
+        'groups.hip: grp_enqueue_head': body('groups.hip', 'static int grp_enqueue_head(', '// Run the groups 0 .. used - 1'),
+        'sweep_core.hip: glx_sweep_launch': body('sweep_core.hip', 'int glx_sweep_launch(', 'int glx_sweep_capture('),
+        'sweep_core.hip: glx_sweep_head_rows': body('sweep_core.hip', 'int glx_sweep_head_rows(', '// Tail: conditional sweeps in chunks.'),
         'cg.hip: reduce': body('cg.hip', 'template <int MODE> int reduce(int i, bool blocks) {', '// x = x0 or 0, r = p = b'),
         'cg.hip: enqueue_iteration + enqueue_chunk': body('cg.hip', 'int enqueue_iteration(int i, bool bl0, bool bl1) {', '// Full chunks are replayed from a captured launch sequence'),
         'cg_fused.hip: enqueue_chunk': body('cg_fused.hip', 'int enqueue_chunk(int iters) {', '// the three chunk lengths as captured launch sequences'),
@@ -376,7 +378,9 @@ def test_captured_launch_sequences_hold_no_memset_node():
     for m in re.finditer(r'run_captured\(s, \{[^}]*\}, \[&\]\(\) -> int \{', text):
         lam = text[m.end():text.index('});', m.end())]
         assert 'hipMemset' not in '\n'.join(line.split('//')[0] for line in lam.splitlines()), lam[:200]
-    assert 'glx_zero_async' in captured['solver.hip: enqueue_head'] and 'glx_zero_async' in captured['groups.hip: grp_launch_sweep + grp_enqueue_head']
+    # both heads clear their stop row through the shared helper, and that helper and the stacked head's reset are kernels
+    assert 'glx_sweep_head_rows' in captured['solver.hip: enqueue_head'] and 'glx_sweep_head_rows' in captured['groups.hip: grp_enqueue_head']
+    assert 'glx_zero_async' in captured['sweep_core.hip: glx_sweep_head_rows'] and 'glx_zero_async' in captured['groups.hip: grp_enqueue_head']
 
 
 def test_block_census_agrees_with_the_walk():
