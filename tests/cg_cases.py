@@ -64,6 +64,10 @@ def _table():
                                rhs='rows', api='rows', out_scale=scale, keep_order=False))
     for C in (3, 17):           # crosses the doubling of rows_per_block (> 262 144 rows) and grp > 32 (> 2048 SpMM workgroups)
         t.append(_case('large-C%d-f64' % C, op='banded', n=300000, C=C, tol=1e-12, max_iter=6, keep_order=False))
+    # the relaxed plan of a state beyond 32 MB with rows split over 4 and 16 slots (75 / 305 entries) in every XCD range beside two
+    # windows of 32 768 rows: tests/test_sell_plan_host.py holds that shape, on the caller's order, which the case therefore keeps
+    # (tau: the Gershgorin bound of cg_ref.banded_hubs, 4 - 3 - 0.3, is 0.7)
+    t.append(_case('large-hubs-C3-f64', op='banded_hubs', n=300000, C=3, tau=0.5, tol=1e-12, max_iter=6, keep_order=True))
     for cap in CAPS:
         t.append(_case('cap-%d-f64' % cap, C=7, max_iter=cap))
     # one DeviceGraph, width / number of systems / cap changing between the solves (the order of the mirror test)
@@ -96,6 +100,8 @@ def _build(case_id, seed):
     rng = np.random.default_rng([seed, n, C])
     if case['op'] == 'banded':
         A = cg_ref.banded(n)
+    elif case['op'] == 'banded_hubs':
+        A = cg_ref.banded_hubs(n)
     else:
         # (a 'sequence' case shares its operator with the others of the sequence: one DeviceGraph)
         A = cg_ref.laplacian_plus(n, 12345 if case.get('sequence') else seed, case['tau'])

@@ -137,6 +137,25 @@ def banded(n):
     return sparse.csr_matrix(sparse.diags(parts, where))
 
 
+HUB_EVERY, HUB_SHORT, HUB_LONG, HUB_WEIGHT = 4096, 70, 300, -0.001
+
+
+def banded_hubs(n):
+    """banded(n) plus symmetric couplings of -0.001 from every 4096th row h (as long as h + 4096 < n) to the rows h + 1500 + 7 j,
+    j < 70 (even hubs) or j < 300 (odd hubs): far from the band, inside the hub's own stretch, so that no row is coupled to two
+    hubs.  Hub rows have 75 / 305 entries (the first: 73), their partners 6; still strictly diagonally dominant (4 > 3 + 0.3)."""
+    hubs = np.arange(0, n - HUB_EVERY, HUB_EVERY)
+    count = np.where((hubs // HUB_EVERY) % 2 == 0, HUB_SHORT, HUB_LONG)
+    h = np.repeat(hubs, count)
+    j = np.arange(len(h)) - np.repeat(np.cumsum(count) - count, count)
+    p = h + 1500 + 7 * j
+    assert p.max() < n and (p - h).max() < HUB_EVERY
+    H = sparse.csr_matrix((np.full(len(h), HUB_WEIGHT), (h, p)), shape=(n, n))
+    A = sparse.csr_matrix(banded(n) + H + H.T)
+    A.sort_indices()
+    return A
+
+
 def in_format(A, dtype):
     """the operator with every entry rounded to `dtype` (what a DeviceGraph of that dtype holds), as an fp64 CSR matrix"""
     A = sparse.csr_matrix(A).copy()
