@@ -110,10 +110,13 @@ def test_device_exp_within_one_ulp(gl, device_exp):
         W = gl.weightmatrix.epsilon_ball(X, eps, features=F, epsilon_f=eps_f)
         want = golden_matrix(g, name, 'gaussian', X.shape[0])
         assert np.array_equal(W.indptr, want.indptr) and np.array_equal(W.indices, want.indices), name
+        from weights_cr_ref import ball_matrix_cr, same_matrix
         if F is None:
             ulps = np.abs(W.data.view(np.int64) - want.data.view(np.int64))
             assert ulps.max() <= 1, (name, int(ulps.max()))
+            assert same_matrix(W, ball_matrix_cr(X.shape[0], ref.prepare(X, eps), eps)), (name, 'bit for bit')
         else:
+            assert same_matrix(W, ball_matrix_cr(X.shape[0], ref.prepare(X, eps, F), eps, eps_f)), (name, 'bit for bit')
             # a product of two exponentials: each factor is within one ulp of numpy's, and the product is checked for what it
             # is -- fl(exp_cr(a) * exp_cr(b)) bit for bit, the factors evaluated one by one through the library's test hook
             assert_product_of_exponentials(W, X, eps, F, eps_f, want, name)

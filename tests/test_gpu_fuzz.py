@@ -159,6 +159,9 @@ def test_random_pipeline_matches_the_oracle(gl, orc, seed, mode):
         # of the smaller entry (tests/test_gpu_weights.py)
         most = 1 if not c['symmetrize'] else (2 if c['kernel'] == 'gaussian' else 8)
         assert int(_ulps(W.data, Wo.data).max(initial=0)) <= most, (tag, int(_ulps(W.data, Wo.data).max()))
+        # no slack is needed: bit for bit the reference's expressions with a correctly rounded exponential
+        from weights_cr_ref import knn_weights_cr, same_matrix
+        assert same_matrix(W, knn_weights_cr(Jo, Do, k, c['kernel'], c['symmetrize'])), tag
     if (not c['symmetrize'] or c['kernel'] in ('distance', 'singular')) and not device:
         # directed graphs / unbounded weights: the sweep is the part of the path defined for them
         W = Wo

@@ -133,6 +133,9 @@ def test_knn_weightmatrix_nosym_and_injected(gl, golden):
             assert np.array_equal(W4.indices, Wg.indices)
             # (a stored weight is the mean of two exponentials: two ulps at most; symgaussian's rule subtracts and carries a few more)
             assert np.max(np.abs(W4.data.view(np.int64) - Wg.data.view(np.int64))) <= (2 if kernel == 'gaussian' else 8), kernel
+            # and bit for bit what the reference's expressions give with a correctly rounded exponential (tests/weights_cr_ref.py)
+            from weights_cr_ref import knn_weights_cr, same_matrix
+            assert same_matrix(W4, knn_weights_cr(kd[0], kd[1], 10, kernel)), kernel
     finally:
         if old is not None:
             os.environ['GLX_HOST_EXP'] = old

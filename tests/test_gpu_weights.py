@@ -99,3 +99,7 @@ def test_symgaussian_and_unsymmetrised_kernels_within_an_ulp():
         Wd, Wh = _both(gl, X, 12, **kw)
         u = _ulps(Wd.data, Wh.data)
         assert u.max() <= most, kw
+        # and the default mode bit for bit: the reference's expressions with a correctly rounded exponential, on the same lists
+        from weights_cr_ref import knn_weights_cr, same_matrix
+        J, D = gl.weightmatrix.knnsearch(X, 13)
+        assert same_matrix(Wd, knn_weights_cr(np.array(J), np.array(D), 12, kw.get('kernel', 'gaussian'), kw.get('symmetrize', True))), kw

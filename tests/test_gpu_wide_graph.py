@@ -12,6 +12,7 @@ from scipy import sparse
 from scipy.sparse import csgraph
 from conftest import blobs
 from test_gpu_fuzz import _virtual_ranks_sweep, _ulps
+from weights_cr_ref import knn_weights_cr, same_matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -222,6 +223,7 @@ def test_boundary_rows_with_the_device_exp(gl, orc, K, n, device_exp):
                 assert np.allclose(W.data, Wo.data, rtol=1e-15, atol=0), (K, kernel, worst)
             else:
                 assert worst <= (2 if symmetrize else 1), (K, kernel, symmetrize, worst)
+            assert same_matrix(W, knn_weights_cr(ind, dist, K - 1, kernel, symmetrize)), (K, kernel, symmetrize, 'bit for bit')
 
 
 BLOCK_CENSUS = {        # K: (smallest M, largest M, rows with M <= 64, with 64 < M <= ROW_CAP, with M > ROW_CAP)
@@ -348,11 +350,13 @@ def test_wide_weight_matrices_with_the_device_exp(gl, orc, blob_lists, k, device
     for kernel in ('gaussian', 'symgaussian'):
         for symmetrize in (True, False):
             Wo = orc.knn_weights(Jo, Do.copy(), k, kernel=kernel, symmetrize=symmetrize)
+            Wc = knn_weights_cr(Jo, Do, k, kernel, symmetrize)
             for W in (gl.weightmatrix.knn(X, k, kernel=kernel, symmetrize=symmetrize),
                       gl.weightmatrix.knn(None, k, kernel=kernel, symmetrize=symmetrize, knn_data=(Jo, Do.copy()))):
                 _same(W, Wo, (k, kernel, symmetrize), exact=False)
                 worst = int(_ulps(W.data, Wo.data).max())
                 assert worst <= (1 if not symmetrize else (2 if kernel == 'gaussian' else 8)), (k, kernel, symmetrize, worst)
+                assert same_matrix(W, Wc), (k, kernel, symmetrize, 'bit for bit')
 
 
 def test_hub_heavy_result_through_ordinary_memory(gl, orc, blob_lists, monkeypatch):
