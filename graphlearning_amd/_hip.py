@@ -154,6 +154,9 @@ _SIGNATURES = {
     'glx_ball_result_destroy': [_vp],
     'glx_ball_stats': [_f64p],
     'glx_sssp': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp, _i64p, _f64p, C.c_int],
+    'glx_components': [C.c_int64, C.c_int64, _vp, _vp, _vp, _i64p, _f64p, C.c_int],
+    'glx_components_set_wave_row': [C.c_int],
+    'glx_components_plan': [_i64p],
     'glx_lip_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_double,
                         _vp, _vp, _vp, _vp, C.c_int, C.c_int],
     'glx_slp_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
@@ -1142,6 +1145,51 @@ def sssp(in_ptr, in_idx, in_cost, src_ptr, src_idx, src_val, max_dist=np.inf, ho
                           _ptr(cp), rounds, ms, _dev(device)), 'glx_sssp')
     sssp_last_ms = tuple(ms)
     return dist, cp, (int(rounds[0]), int(rounds[1]))
+
+
+components_last_ms = None       # host milliseconds of the last call: uploads, checks, kernels, downloads
+
+
+def int32_index_array(a, name):
+    """`a` as a contiguous int32 array; ValueError if a value does not fit (a cast would wrap it into range)"""
+    a = np.asarray(a)
+    if a.dtype != np.int32:
+        if a.dtype.kind not in 'iu':
+            raise ValueError('%s: an integer array is expected, not %s' % (name, a.dtype))
+        if a.size and (int(a.min()) < -(1 << 31) or int(a.max()) > (1 << 31) - 1):
+            raise ValueError('%s holds values that are not int32-representable' % name)
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def components(indptr, indices, n, device=None):
+    """Connected components of the pattern of an n x n CSR matrix given by its raw index arrays (glx_components, csrc/cc.hip): every
+    stored entry joins its row and its column, whatever its value.  Returns (ncomp, labels int32 (n,)) with scipy's numbering --
+    components in the order of their smallest vertex.  Malformed arrays are refused with GlxError before a kernel follows an index."""
+    global components_last_ms
+    indptr = int32_index_array(indptr, 'indptr')
+    indices = int32_index_array(indices, 'indices')
+    n = int(n)
+    if n < 1 or indptr.ndim != 1 or indices.ndim != 1 or len(indptr) != n + 1:
+        raise GlxError('components: indptr has %s entries for n = %d' % (indptr.shape, n))
+    labels = np.empty(n, dtype=np.int32)
+    ncomp = C.c_int64(0)
+    ms = (C.c_double * 4)(0, 0, 0, 0)
+    check(load().glx_components(n, len(indices), _ptr(indptr), _ptr(indices), _ptr(labels), C.byref(ncomp), ms, _dev(device)),
+          'glx_components')
+    components_last_ms = tuple(ms)
+    return int(ncomp.value), labels
+
+
+def components_set_wave_row(min_entries=0):
+    """plan override of the calling thread for measurements: rows of at least `min_entries` stored entries take a wavefront (0: the library's)"""
+    check(load().glx_components_set_wave_row(int(min_entries)), 'glx_components_set_wave_row')
+
+
+def components_plan():
+    """(threshold in effect, the library's own, vertices per scan tile, rows that took a wavefront in this thread's last call)"""
+    out = (C.c_int64 * 4)()
+    check(load().glx_components_plan(out), 'glx_components_plan')
+    return tuple(int(v) for v in out)
 
 
 def lip_iterate(n, nbr, row, W, ind, val, weighted, alpha, beta, T, tol, device=None, want_errors=False, small_level=-1):

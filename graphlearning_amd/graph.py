@@ -519,8 +519,33 @@ class graph:
         return graph(W[ind, :][:, ind])
 
     def isconnected(self):
+        """On the host (scipy), so it works without a GPU; `connected_components()[0] == 1` is the same answer from the device."""
         from scipy.sparse import csgraph
         return csgraph.connected_components(self.weight_matrix)[0] == 1
+
+    def connected_components(self, device=None):
+        """(ncomp, labels int32 (n,)): the connected components of the weight matrix's pattern, found on the GPU (csrc/cc.hip; DESIGN.md
+        4.16).  Every stored entry joins its two vertices whatever its direction and value, so the result equals
+        `scipy.sparse.csgraph.connected_components(W, directed=False)` -- and the default weak form `isconnected` uses -- on every
+        vertex: components are numbered by their smallest vertex.  There is no strong connectivity.  The matrix is taken as
+        `W.tocsr()` yields it (unsorted rows, duplicates and stored zeros included)."""
+        from . import _hip
+        W = self.weight_matrix.tocsr()
+        if W.ndim != 2 or W.shape[0] != W.shape[1] or W.shape[0] < 1:
+            raise ValueError('connected_components needs a square weight matrix, got shape %s' % (W.shape,))
+        indptr = _hip.int32_index_array(W.indptr, 'the weight matrix: indptr')
+        indices = _hip.int32_index_array(W.indices, 'the weight matrix: indices')
+        return _hip.components(indptr, indices, W.shape[0], device=device)
+
+    def largest_connected_component(self, device=None):
+        """(G, ind) as the reference returns them (graph.py:553-582): the graph restricted to its largest connected component and the
+        bool mask of that component's vertices; among components of equal size the first one (the one with the smallest vertex) wins.
+        The components come from the GPU; the restriction `W[ind, :][:, ind]` is the reference's own scipy expression on the host."""
+        ncomp, labels = self.connected_components(device=device)
+        ind = labels == np.argmax(np.bincount(labels, minlength=ncomp))
+        A = self.weight_matrix[ind, :]
+        A = A[:, ind]
+        return graph(A), ind
 
 
 # the reference exposes the class as `graphlearning.graph` (its __init__ rebinds the name of this

@@ -194,6 +194,24 @@ int glx_sssp(int64_t n, int64_t nnz, const int64_t* in_ptr, const int32_t* in_id
              const double* src_val, double max_dist, int form, double* dist, int32_t* cp, int64_t* rounds_out, double* ms_out,
              int device);
 
+/* ---- connected components: graph.connected_components / largest_connected_component (csrc/cc.hip, csrc/cc_plan.h) -----------------
+ * The components of the PATTERN of a CSR matrix: every stored entry (i, j) with i != j joins i and j, whatever its direction and value
+ * (a stored zero is an entry; rows may be unsorted and hold duplicates; a graph with no entries has n components).  Lock-free
+ * union-find in one pass (the argument heads csrc/cc.hip); labels (n) <- the component of every vertex, components numbered by their
+ * smallest vertex in ascending order: the labels of scipy.sparse.csgraph.connected_components(W, directed=False), and of its default
+ * weak form, on every vertex.  *ncomp_out <- the number of components.  ms_out[4] (or NULL): host milliseconds of the uploads, the
+ * checks (row pointers on the host, column indices on the device), the kernels and the downloads.  n >= 1, nnz >= 0, both at most
+ * 2^31 - 1 (GLX_EUNSUPPORTED beyond).  All pointers are host pointers; the caller owns the buffers.  GLX_EINVAL, before any kernel
+ * follows an index: a null argument, rowptr[0] != 0, rowptr[n] != nnz, row pointers that decrease, a column index outside [0, n).
+ * glx_components_set_wave_row: a plan override of the calling thread for measurements -- rows of at least that many stored entries
+ * take a wavefront, shorter ones a thread (0: the library's CC_WAVE_ROW).  No result depends on it.
+ * glx_components_plan: out[4] <- the threshold in effect, the library's own, the vertices per tile of the numbering's prefix sum, the
+ * rows that took a wavefront in the calling thread's last glx_components. */
+int glx_components(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int32_t* labels, int64_t* ncomp_out,
+                   double* ms_out, int device);
+int glx_components_set_wave_row(int min_entries);
+int glx_components_plan(int64_t out[4]);
+
 /* ---- in-order Gauss-Seidel sweeps: graph.amle / ssl.amle (csrc/lip.hip, csrc/lip_plan.h) ---------------------------------------------
  * lip_iterate_main (weighted = 0) and lip_iterate_weighted_main (weighted != 0) of the reference's C extension
  * (c_code/lp_iterate.cpp:129-259) bit for bit: the sequential sweep in vertex order runs as the levels of its dependence pattern,
