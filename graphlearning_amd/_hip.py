@@ -164,6 +164,8 @@ _SIGNATURES = {
                              C.c_int],
     'glx_ck_solve': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp,
                      _f64p, _i64p, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
+    'glx_dlp_solve': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp,
+                      C.c_int],
     'glx_mmbo_solve': [C.c_int64, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, _vp, _vp, _vp,
                        C.c_int],
     'glx_eig_create': [C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
@@ -1288,6 +1290,29 @@ def ck_solve(row_ptr, col, W, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e
 
 
 _CK_ITERATE_FN = C.CFUNCTYPE(C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_double, _vp)
+
+
+def dlp_solve(row_ptr, col, P, ind, val, alpha=0.05, lam=0.1, T=2, device=None, want_history=False):
+    """Dynamic label propagation in one device call and without the dense n x n array (glx_dlp_solve, csrc/dlp.hip; the contract is
+    DESIGN.md 4.17): P as canonical CSR arrays (row_ptr, col, P), the training vertices `ind` with their rows `val` (m, k).  Returns
+    (u_T (n, k) float64, hist (T, n, k) = u_1 .. u_T or None, plan = (launches enqueued, sparse passes, Gram passes, partial sums per
+    Gram entry))."""
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    ind = np.ascontiguousarray(ind, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    n, T = len(row_ptr) - 1, int(T)
+    if (row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or P.shape != col.shape or ind.ndim != 1 or val.ndim != 2 or val.shape[0] != len(ind)
+            or val.shape[1] < 1):
+        raise GlxError('dlp_solve: inconsistent array shapes or sizes')
+    k = int(val.shape[1])
+    u = np.empty((n, k), dtype=np.float64)
+    hist = np.empty((T, n, k), dtype=np.float64) if (want_history and 1 <= T <= 64) else None
+    plan = (C.c_int64 * 4)(0, 0, 0, 0)
+    check(load().glx_dlp_solve(n, len(col), _ptr(row_ptr), _ptr(col), _ptr(P), k, len(ind), _ptr(ind), _ptr(val), float(alpha), float(lam), T,
+                               _ptr(u), _ptr(hist) if hist is not None else None, plan, _dev(device)), 'glx_dlp_solve')
+    return u, hist, tuple(int(v) for v in plan)
 
 
 def mmbo_solve(X, vals, lab0, ind, lab, k, Ns=6, T=10, dt=0.15, mu=50, device=None):

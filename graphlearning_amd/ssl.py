@@ -1464,6 +1464,98 @@ class centered_kernel(ssl):
         return u
 
 
+DLP_MAX_CLASSES, DLP_MAX_T, DLP_MAX_WORK = 64, 64, 1 << 30       # csrc/dlp_plan.h: columns, steps, (2 T + 2) n k values of workspace
+DLP_HISTORY_BYTES = 1 << 30       # dynamic_label_propagation with all_labels: the iterates (T, n, k) the device call hands back, at most
+
+
+class dynamic_label_propagation(ssl):
+    def __init__(self, W=None, class_priors=None, alpha=0.05, lam=0.1, T=2):
+        """Dynamic label propagation (reference ssl.py:1263-1343; Wang, Tu and Tsotsos, ICCV 2013): T steps of v = P u; u = Pt u;
+        u[train] = K; Pt = P Pt P^T + alpha v v^T + lam I with P = D^-1 W and Pt = P at first, all classes as the columns of one
+        device call (_hip.dlp_solve; the contract is DESIGN.md 4.17).  Not one-vs-rest.  The reference holds Pt as a dense n x n
+        array and refuses n > 5000 (it prints a line and returns the one-hot start); here Pt is applied through its unrolled
+        recursion -- T^2 + max(T - 2, 0) sparse products and T (T - 1) / 2 Gram matrices of size k x k -- so graphs of any size
+        within the workspace cap are solved.  The diagonal is removed and P = degree_matrix(p=-1) * W is formed on the host by
+        the reference's own expressions; the sums over all vertices of v^T X follow a fixed order where the reference's belong to
+        the host's BLAS: `prob` equals the reference's to a measured 1e-15 or so of its largest entry, and the
+        result is a pure function of the inputs.  After a fit: `num_iter` (= T) and `dlp_plan`.  With `all_labels` the reference's
+        line `Accuracy = ..` per iteration is printed after the solve, from the iterates the call returns.  Refused with
+        ValueError before any device call: a vertex whose degree is 0 once the diagonal is removed (the reference divides by
+        zero), a weight that is NaN or infinite or a reciprocal degree that is not finite, T < 1 or T > 64, alpha or lam not
+        finite, a training index out of range, labels that are not exactly 0 .. k-1, index and label arrays of different
+        lengths, an empty training set, more than 64 classes, (2 T + 2) n k above 2^30 values of workspace, an all_labels
+        history above 1 GiB.  Negative weights and an unsymmetric W are legal."""
+        super().__init__(W, class_priors)
+        self.alpha = alpha
+        self.lam = lam
+        self.T = T
+        self.accuracy_filename = '_dynamic_label_propagation'
+        self.name = 'Dynamic Label Propagation'
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        n = self.graph.num_nodes
+        train_ind = np.asarray(train_ind).ravel()
+        train_labels = np.asarray(train_labels).ravel()
+        T = self.T
+        if not (T == int(T) and 1 <= int(T) <= DLP_MAX_T):
+            raise ValueError('dynamic_label_propagation: T=%r must be a whole number from 1 to %d' % (T, DLP_MAX_T))
+        T = int(T)
+        if not (np.isfinite(self.alpha) and np.isfinite(self.lam)):
+            raise ValueError('dynamic_label_propagation: alpha=%r or lam=%r is not finite' % (self.alpha, self.lam))
+        if len(train_ind) != len(train_labels):
+            raise ValueError('dynamic_label_propagation: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
+        if len(train_ind) == 0:
+            raise ValueError('dynamic_label_propagation: no training vertex')
+        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
+            raise ValueError('dynamic_label_propagation: train_ind out of range (or not an integer array)')
+        classes = np.unique(train_labels)
+        k = len(classes)
+        if not np.array_equal(classes, np.arange(k)):
+            raise ValueError('dynamic_label_propagation: the labels are not exactly 0 .. %d' % (k - 1))
+        if k > DLP_MAX_CLASSES:
+            raise ValueError('dynamic_label_propagation: %d classes, at most %d columns per call' % (k, DLP_MAX_CLASSES))
+        if (2 * T + 2) * n * k > DLP_MAX_WORK:
+            raise ValueError('dynamic_label_propagation: (2 T + 2) n k = %d values of workspace (T=%d, n=%d, k=%d), above the limit of %d'
+                             % ((2 * T + 2) * n * k, T, n, k, DLP_MAX_WORK))
+        want_hist = all_labels is not None
+        if want_hist and T * n * k * 8 > DLP_HISTORY_BYTES:
+            raise ValueError('dynamic_label_propagation: the iterates of an all_labels fit take %d bytes (T=%d x n=%d x k=%d doubles), '
+                             'above the limit of %d' % (T * n * k * 8, T, n, k, DLP_HISTORY_BYTES))
+        W = self.graph.weight_matrix
+        W = sparse.csr_matrix(W - sparse.spdiags(W.diagonal(), 0, n, n), dtype=np.float64)      # the diagonal goes as in the reference
+        W.sum_duplicates()
+        W.eliminate_zeros()
+        W.sort_indices()
+        if not np.all(np.isfinite(W.data)):
+            raise ValueError('dynamic_label_propagation: a weight is NaN or infinite')
+        G = graph_mod.graph(W)
+        lonely = np.where(G.degree_vector() == 0)[0]
+        if len(lonely):
+            raise ValueError('dynamic_label_propagation: vertex %d has degree 0 once the diagonal is removed (the reference divides by '
+                             'zero there)' % int(lonely[0]))
+        with np.errstate(over='ignore'):
+            D = G.degree_matrix(p=-1)
+        if not np.all(np.isfinite(D.diagonal())):
+            raise ValueError('dynamic_label_propagation: a reciprocal degree is not finite')
+        P = sparse.csr_matrix(D * W)
+        P.sort_indices()
+        if not np.all(np.isfinite(P.data)):
+            raise ValueError('dynamic_label_propagation: an entry of P = D^-1 W is not finite')
+        # rows listed twice: the device call gives a vertex its last row, as the reference's assignment u[train_ind, :] = K does
+        val = (train_labels.astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
+        u, hist, plan = _hip.dlp_solve(P.indptr.astype(np.int64), P.indices.astype(np.int32), P.data, train_ind.astype(np.int32), val,
+                                       alpha=float(self.alpha), lam=float(self.lam), T=T, device=self.device, want_history=want_hist)
+        self.num_iter = T
+        self.dlp_plan = plan
+        if want_hist:                     # the reference's lines (ssl.py:1335-1339), one per iteration, on each iterate
+            for i in range(T):
+                self.prob = hist[i]
+                acc = ssl_accuracy(self.predict(), all_labels, train_ind)
+                sys.stdout.write('Accuracy = %.2f\n' % acc)
+            sys.stdout.flush()
+        return u
+
+
 MMBO_CAP = 4096          # classes times eigenvectors at most (csrc/mmbo_plan.h: Z is held in LDS)
 
 

@@ -364,6 +364,25 @@ int glx_incres_stats(glx_incres* h, int64_t* out);
 int glx_incres_destroy(glx_incres* h);
 int glx_host_group_by_label(int64_t n, const int32_t* labels, int k, int64_t* counts, int32_t* order);
 
+/* ---- dynamic label propagation: ssl.dynamic_label_propagation (csrc/dlp.hip, csrc/dlp_plan.h) -------------------------------------
+ * The loop of the reference's ssl.dynamic_label_propagation (ssl.py:1328-1332; Wang, Tu and Tsotsos, ICCV 2013) in one blocking call
+ * and without its dense n x n array: T steps of v = P u; u = Pt u; u[ind] = val; Pt = P Pt P^T + alpha v v^T + lam I (Pt = P at
+ * first), with Pt applied through the unrolled recursion Pt_t X = P (Pt_{t-1} (P^T X)) + alpha v_{t-1} (v_{t-1}^T X) + lam X --
+ * T^2 + max(T - 2, 0) sparse products of (n, k) blocks and T (T - 1) / 2 Gram matrices of size k x k per call, (2 T + 2) n k values
+ * of workspace.  The order of operations and of every sum is that of DESIGN.md 4.17, so the result is a pure function of the
+ * arguments (no floating-point atomics, no fused multiply-add) and equals dlp_host_reference (csrc/dlp_plan.h) bit for bit; alpha == 0
+ * and lam == 0 take no shortcut.  P arrives as canonical CSR: n rows, M entries, row_ptr (n + 1), col strictly ascending inside a row,
+ * values finite, of either sign; empty rows and a stored diagonal are legal; P^T is built inside the call.  u starts from val (m, k)
+ * row-major on the m training vertices ind (a vertex listed twice takes its last row) and from zero elsewhere, and the training rows
+ * are set back to val after every step.  u (n, k) row-major: u_T.  hist (or NULL), (T, n, k): u_1 .. u_T.  plan_out[4] (or NULL): the
+ * launches enqueued, the sparse passes, the Gram passes, the partial sums per Gram entry.  The host reads nothing back between the
+ * steps.  All pointers are host pointers.
+ * GLX_EINVAL: a null argument, bad sizes, rows that are not canonical, an index out of range, a value that is not finite, T < 1, alpha or
+ * lam not finite.  GLX_EUNSUPPORTED: k > 64 (the Gram is held in LDS), T > 64, (2 T + 2) n k > 2^30. */
+int glx_dlp_solve(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* P, int k, int64_t m,
+                  const int32_t* ind, const double* val, double alpha, double lam, int64_t T, double* u, double* hist,
+                  int64_t* plan_out, int device);
+
 #ifdef __cplusplus
 }
 #endif
