@@ -1221,20 +1221,29 @@ def lip_iterate(n, nbr, row, W, ind, val, weighted, alpha, beta, T, tol, device=
     return u, iters, (int(plan[0]), int(plan[1]), int(plan[2])), errs
 
 
+def _csr_operands(row_ptr, col, entries, ind=None, val=None):
+    """The arrays of a one-call solver as the library takes them: (ok, n, row_ptr int64, col int32, the per-entry arrays float64, ind
+    int32, val float64), all contiguous.  ok: row_ptr is (n + 1) with n >= 1, col (M), every per-entry array (M), and -- where given --
+    ind (m) and val (m, k) with k >= 1.  The caller adds its own conditions and raises its own GlxError."""
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    entries = [np.ascontiguousarray(a, dtype=np.float64) for a in entries]
+    n = len(row_ptr) - 1
+    ok = row_ptr.ndim == 1 and n >= 1 and col.ndim == 1 and all(a.shape == col.shape for a in entries)
+    if ind is not None:
+        ind = np.ascontiguousarray(ind, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        ok = ok and ind.ndim == 1 and val.ndim == 2 and val.shape[0] == len(ind) and val.shape[1] >= 1
+    return (ok, n, row_ptr, col, *entries, ind, val)
+
+
 def slp_iterate(row_ptr, col, W, lam, gamma, ind, val, T, device=None, want_history=False):
     """T iterations of sparse label propagation on the GPU (glx_slp_iterate, csrc/slp.hip; the contract is DESIGN.md 4.9): W as
     canonical CSR arrays (row_ptr, col, W), lam per entry, gamma per vertex, the labelled vertices `ind` and the rows `val` (m, C) they are
     set to.  Returns (u (n, C) float64, the iterates (T, n, C) or None, plan = (launches per iteration, launches enqueued, column tile))."""
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    col = np.ascontiguousarray(col, dtype=np.int32)
-    W = np.ascontiguousarray(W, dtype=np.float64)
-    lam = np.ascontiguousarray(lam, dtype=np.float64)
-    gamma = np.ascontiguousarray(gamma, dtype=np.float64)
-    ind = np.ascontiguousarray(ind, dtype=np.int32)
-    val = np.ascontiguousarray(val, dtype=np.float64)
-    n, T = len(row_ptr) - 1, int(T)
-    if (row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or W.shape != col.shape or lam.shape != col.shape or gamma.shape != (n,) or ind.ndim != 1
-            or val.ndim != 2 or val.shape[0] != len(ind) or val.shape[1] < 1 or T < 0):
+    ok, n, row_ptr, col, W, lam, ind, val = _csr_operands(row_ptr, col, (W, lam), ind, val)
+    gamma, T = np.ascontiguousarray(gamma, dtype=np.float64), int(T)
+    if not (ok and gamma.shape == (n,) and T >= 0):
         raise GlxError('slp_iterate: inconsistent array shapes or sizes')
     Cc = int(val.shape[1])
     u = np.empty((n, Cc), dtype=np.float64)
@@ -1252,15 +1261,9 @@ def ck_solve(row_ptr, col, W, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e
     iteration, launches enqueued, iterations per chunk, partial sums per column)).  on_iterate(q, u_q, err_q), if given, is called after
     every iteration with a view of the iterate that is valid during the call only; the solve then runs one iteration per chunk and
     downloads every iterate (slow).  GlxError when max_it iterations pass without a stop."""
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    col = np.ascontiguousarray(col, dtype=np.int32)
-    W = np.ascontiguousarray(W, dtype=np.float64)
-    ind = np.ascontiguousarray(ind, dtype=np.int32)
-    val = np.ascontiguousarray(val, dtype=np.float64)
+    ok, n, row_ptr, col, W, ind, val = _csr_operands(row_ptr, col, (W,), ind, val)
     e = np.ascontiguousarray(e, dtype=np.float64).ravel()
-    n = len(row_ptr) - 1
-    if (row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or W.shape != col.shape or ind.ndim != 1 or val.ndim != 2 or val.shape[0] != len(ind)
-            or val.shape[1] < 1 or e.shape != (n,) or int(err_cap) < 0):
+    if not (ok and e.shape == (n,) and int(err_cap) >= 0):
         raise GlxError('ck_solve: inconsistent array shapes or sizes')
     k = int(val.shape[1])
     u = np.empty((n, k), dtype=np.float64)
@@ -1297,14 +1300,9 @@ def dlp_solve(row_ptr, col, P, ind, val, alpha=0.05, lam=0.1, T=2, device=None, 
     DESIGN.md 4.17): P as canonical CSR arrays (row_ptr, col, P), the training vertices `ind` with their rows `val` (m, k).  Returns
     (u_T (n, k) float64, hist (T, n, k) = u_1 .. u_T or None, plan = (launches enqueued, sparse passes, Gram passes, partial sums per
     Gram entry))."""
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    col = np.ascontiguousarray(col, dtype=np.int32)
-    P = np.ascontiguousarray(P, dtype=np.float64)
-    ind = np.ascontiguousarray(ind, dtype=np.int32)
-    val = np.ascontiguousarray(val, dtype=np.float64)
-    n, T = len(row_ptr) - 1, int(T)
-    if (row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or P.shape != col.shape or ind.ndim != 1 or val.ndim != 2 or val.shape[0] != len(ind)
-            or val.shape[1] < 1):
+    ok, n, row_ptr, col, P, ind, val = _csr_operands(row_ptr, col, (P,), ind, val)
+    T = int(T)
+    if not ok:
         raise GlxError('dlp_solve: inconsistent array shapes or sizes')
     k = int(val.shape[1])
     u = np.empty((n, k), dtype=np.float64)
@@ -1347,11 +1345,8 @@ class Eig:
 
     def __init__(self, row_ptr, col, val, m, device=None):
         self._h = _vp()
-        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        col = np.ascontiguousarray(col, dtype=np.int32)
-        val = np.ascontiguousarray(val, dtype=np.float64)
-        n = len(row_ptr) - 1
-        if row_ptr.ndim != 1 or n < 1 or col.ndim != 1 or val.shape != col.shape or (n >= 1 and int(row_ptr[-1]) != len(col)):
+        ok, n, row_ptr, col, val, _, _ = _csr_operands(row_ptr, col, (val,))
+        if not (ok and int(row_ptr[-1]) == len(col)):
             raise GlxError('Eig: inconsistent array shapes or sizes')
         self.n, self.m = n, int(m)
         check(load().glx_eig_create(n, _ptr(row_ptr), _ptr(col), _ptr(val), int(m), _dev(device), C.byref(self._h)), 'glx_eig_create')

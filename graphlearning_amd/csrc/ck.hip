@@ -98,7 +98,8 @@ __global__ __launch_bounds__(FS_ROWS * CK_TILE) void ck_pass_kernel(const int64_
   if (ck_stopped(slots[r_slot - 1], tol)) return;          // the iteration before was the last one
   const int r = (int)threadIdx.x / ct, c = (int)threadIdx.x - r * ct;
   const int tile = blockIdx.y;
-  const int c0 = tile * tbase + (tile < textra ? tile : textra), cols = tbase + (tile < textra ? 1 : 0);
+  const ColTile tl = col_tile_at(tile, tbase, textra);
+  const int c0 = tl.c0, cols = tl.cols;
   const int64_t i = (int64_t)blockIdx.x * FS_ROWS + r;
   if (threadIdx.x == 0) s_e = 0ull;
   double v[2] = {0.0, 0.0};
@@ -288,7 +289,7 @@ extern "C" int glx_ck_solve(int64_t n, int64_t M, const int64_t* row_ptr, const 
   GLX_HIP(hipGetLastError());
   launches += 2;
 
-  const int tbase = k / plan.ntiles, textra = k % plan.ntiles;          // ck_tile: tile t starts at t * tbase + min(t, textra)
+  const int tbase = k / plan.ntiles, textra = k % plan.ntiles;          // what col_tile_at (csr_plan.h) takes
   const dim3 grid((unsigned)P, (unsigned)plan.ntiles), blk((unsigned)(FS_ROWS * plan.ct));
   const size_t lds = (size_t)2 * FS_ROWS * plan.ct * 8;
   std::vector<double> iterate;

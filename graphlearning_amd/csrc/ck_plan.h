@@ -23,6 +23,7 @@
 // the very start).  A pass and its finishing kernel first look at the slot before theirs and do nothing when !(slot > tol): after the
 // stop every later slot stays NaN, which stops as well, whatever tol is.
 #pragma once
+#include "csr_plan.h"
 #include "fixed_sum.h"
 #include <cmath>
 #include <cstddef>
@@ -44,23 +45,13 @@ struct CkPlan {
   int ntiles = 0, ct = 0;                  // column tiles of the pass and the widest tile's columns
 };
 
-// the column tiles of the pass: at most CK_TILE columns each, widths within one of each other, the widest first
-inline void ck_tiles(int k, int* ntiles, int* ct) {
-  *ntiles = (k + CK_TILE - 1) / CK_TILE;
-  *ct = (k + *ntiles - 1) / *ntiles;
-}
-// first column and width of tile t
-inline void ck_tile(int k, int t, int* c0, int* cols) {
-  int nt, ct;
-  ck_tiles(k, &nt, &ct);
-  const int base = k / nt, extra = k % nt;
-  *c0 = t * base + (t < extra ? t : extra);
-  *cols = base + (t < extra ? 1 : 0);
-}
+// the column tiles of the pass: the tile rule of csr_plan.h with at most CK_TILE columns each
+inline void ck_tiles(int k, int* ntiles, int* ct) { col_tiles(k, CK_TILE, ntiles, ct); }
+inline void ck_tile(int k, int t, int* c0, int* cols) { col_tile(k, CK_TILE, t, c0, cols); }
 
-// 0, or a message in `msg` and: 1 sizes, 2 row pointers, 3 a column index out of range, 4 a row that is not canonical, 5 a stored
-// diagonal entry, 6 a weight that is not finite, 7 a training vertex out of range, 8 power_it, alpha_frac or max_it, 9 unsupported
-// (k above CK_MAX_COLS, n * k above 2^31)
+// 0, or a message in `msg` and: 1 sizes, 2 row pointers, 3 a column index out of range, 4 a row with columns not strictly ascending,
+// 5 a stored diagonal entry, 6 a weight that is not finite, 7 a training vertex out of range, 8 power_it, alpha_frac or max_it,
+// 9 unsupported (k above CK_MAX_COLS, n * k above 2^31)
 inline int ck_validate(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* W, int k, int64_t m, const int32_t* ind,
                        int64_t power_it, double alpha_frac, int64_t max_it, char* msg, size_t cap) {
   if (n < 1 || n > 0x7fffffffll || M < 0 || M > 0x7fffffffll || m < 0 || k < 1) {
@@ -76,41 +67,18 @@ inline int ck_validate(int64_t n, int64_t M, const int64_t* row_ptr, const int32
              alpha_frac);
     return 8;
   }
-  if (row_ptr[0] != 0 || row_ptr[n] != M) {
-    snprintf(msg, cap, "row pointers run from %lld to %lld, expected 0 to M=%lld", (long long)row_ptr[0], (long long)row_ptr[n], (long long)M);
-    return 2;
-  }
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t e0 = row_ptr[i], e1 = row_ptr[i + 1];
-    if (e1 < e0 || e1 > M) {
-      snprintf(msg, cap, "row pointers of vertex %lld are not ascending within [0, M]", (long long)i);
-      return 2;
+  const int bad = csr_walk(n, M, row_ptr, col, 2, 3, 4, msg, cap, [&](int64_t i, int64_t e) {
+    if (col[e] == i) {
+      snprintf(msg, cap, "row %lld stores its diagonal entry (the caller removes the diagonal)", (long long)i);
+      return 5;
     }
-    for (int64_t e = e0; e < e1; ++e) {
-      if (col[e] < 0 || col[e] >= n) {
-        snprintf(msg, cap, "column index %d of entry %lld out of range", col[e], (long long)e);
-        return 3;
-      }
-      if (e > e0 && col[e - 1] >= col[e]) {
-        snprintf(msg, cap, "row %lld is not canonical: its columns are not strictly ascending (entry %lld)", (long long)i, (long long)e);
-        return 4;
-      }
-      if (col[e] == i) {
-        snprintf(msg, cap, "row %lld stores its diagonal entry (the caller removes the diagonal)", (long long)i);
-        return 5;
-      }
-      if (!std::isfinite(W[e])) {
-        snprintf(msg, cap, "weight %g of entry %lld is not finite", W[e], (long long)e);
-        return 6;
-      }
+    if (!std::isfinite(W[e])) {
+      snprintf(msg, cap, "weight %g of entry %lld is not finite", W[e], (long long)e);
+      return 6;
     }
-  }
-  for (int64_t q = 0; q < m; ++q)
-    if (ind[q] < 0 || ind[q] >= n) {
-      snprintf(msg, cap, "training vertex %d out of range", ind[q]);
-      return 7;
-    }
-  return 0;
+    return 0;
+  });
+  return bad ? bad : csr_check_vertices(ind, m, n, 7, "training", msg, cap);
 }
 
 inline void ck_make_plan(int64_t n, const int64_t* row_ptr, const int32_t* col, const double* W, int k, int64_t m, const int32_t* ind,
@@ -130,8 +98,7 @@ inline void ck_make_plan(int64_t n, const int64_t* row_ptr, const int32_t* col, 
   for (int64_t j = 0; j < n; ++j) sc = sc + P.c[j];
   P.sc = sc;
   P.invn = 1.0 / (double)n;
-  P.lab.assign((size_t)n, -1);
-  for (int64_t q = 0; q < m; ++q) P.lab[ind[q]] = (int32_t)q;
+  P.lab = csr_label_rows(n, m, ind);
   P.P = fs_partials(n);
   ck_tiles(k, &P.ntiles, &P.ct);
 }

@@ -39,8 +39,8 @@ __global__ __launch_bounds__(FS_ROWS * DLP_TILE) void dlp_pass_kernel(const int6
     __syncthreads();
   }
   const int r = (int)threadIdx.x / ct, c = (int)threadIdx.x - r * ct;
-  const int tile = blockIdx.y;
-  const int c0 = tile * tbase + (tile < textra ? tile : textra), cols = tbase + (tile < textra ? 1 : 0);
+  const ColTile tl = col_tile_at((int)blockIdx.y, tbase, textra);
+  const int c0 = tl.c0, cols = tl.cols;
   const int64_t i = (int64_t)blockIdx.x * FS_ROWS + r;
   if (i >= n || c >= cols) return;
   const int b = c0 + c;
@@ -77,8 +77,8 @@ __global__ __launch_bounds__(DLP_GRAM_THREADS) void dlp_gram_kernel(const double
   extern __shared__ __attribute__((aligned(16))) double s_t[];          // X: k columns, then V: ct columns, DLP_GRAM_LD doubles each
   double* s_x = s_t;
   double* s_v = s_t + (size_t)k * DLP_GRAM_LD;
-  const int tile = blockIdx.y;
-  const int c0 = tile * tbase + (tile < textra ? tile : textra), cols = tbase + (tile < textra ? 1 : 0);
+  const ColTile tl = col_tile_at((int)blockIdx.y, tbase, textra);
+  const int c0 = tl.c0, cols = tl.cols;
   const int64_t p = blockIdx.x, i0 = p * FS_ROWS;
   // rows past n count as +0.0
   for (int q = threadIdx.x; q < FS_ROWS * k; q += DLP_GRAM_THREADS) {
@@ -166,7 +166,7 @@ extern "C" int glx_dlp_solve(int64_t n, int64_t M, const int64_t* row_ptr, const
   double* const d_R = d_Y + (size_t)(T - 1) * nk;
   auto iterate = [&](int64_t t) { return t > 0 && d_hist ? d_hist + (size_t)(t - 1) * nk : d_work + (size_t)(t & 1) * nk; };
 
-  const int tbase = k / plan.ntiles, textra = k % plan.ntiles;
+  const int tbase = k / plan.ntiles, textra = k % plan.ntiles;          // what col_tile_at (csr_plan.h) takes
   const dim3 grid((unsigned)plan.P, (unsigned)plan.ntiles), blk((unsigned)(FS_ROWS * plan.ct));
   const size_t gram_lds = (size_t)(k + plan.ct) * DLP_GRAM_LD * 8;
   int64_t launches = 0, sparse = 0, grams = 0;

@@ -26,6 +26,7 @@
 //   Nothing skipped   alpha == 0 and lam == 0 take no shortcut, the terms are evaluated as written; no test for non-finite values.
 // A fit enqueues T^2 + max(T - 2, 0) sparse passes (the second term: the v_t of the steps 1 .. T-2) and T (T - 1) / 2 Grams.
 #pragma once
+#include "csr_plan.h"
 #include "fixed_sum.h"
 #include <cmath>
 #include <cstddef>
@@ -44,21 +45,14 @@ struct DlpPlan {
   std::vector<double> tval;                // (M)
   std::vector<int32_t> lab;                // (n) the row of `val` a training vertex is set to (the last one that lists it), -1 elsewhere
   int64_t P = 0;                           // partials per Gram entry: fs_partials(n)
-  int ntiles = 0, ct = 0;                  // column tiles of the sparse pass and the widest tile's columns
+  int ntiles = 0, ct = 0;                  // column tiles of the sparse pass (csr_plan.h, at most DLP_TILE columns) and the widest's columns
   int64_t work = 0;                        // values of workspace: (2 T + 2) n k
   int64_t sparse = 0, grams = 0;           // sparse passes and Gram passes of the fit
 };
 
-// the column tiles: at most DLP_TILE columns each, widths within one of each other, the widest first (tile t starts at
-// t * (k / ntiles) + min(t, k % ntiles))
-inline void dlp_tiles(int k, int* ntiles, int* ct) {
-  *ntiles = (k + DLP_TILE - 1) / DLP_TILE;
-  *ct = (k + *ntiles - 1) / *ntiles;
-}
-
-// 0, or a message in `msg` and: 1 sizes, 2 row pointers, 3 a column index out of range, 4 a row that is not canonical, 5 a value that
-// is not finite, 6 a training vertex out of range, 7 T below 1, or alpha or lam not finite, 9 unsupported (k above DLP_MAX_COLS, T above
-// DLP_MAX_T, (2 T + 2) n k above DLP_MAX_WORK)
+// 0, or a message in `msg` and: 1 sizes, 2 row pointers, 3 a column index out of range, 4 a row with columns not strictly ascending,
+// 5 a value that is not finite, 6 a training vertex out of range, 7 T below 1, or alpha or lam not finite, 9 unsupported (k above
+// DLP_MAX_COLS, T above DLP_MAX_T, (2 T + 2) n k above DLP_MAX_WORK)
 inline int dlp_validate(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* P, int k, int64_t m, const int32_t* ind,
                         double alpha, double lam, int64_t T, char* msg, size_t cap) {
   if (n < 1 || n > 0x7fffffffll || M < 0 || M > 0x7fffffffll || m < 0 || k < 1) {
@@ -74,37 +68,12 @@ inline int dlp_validate(int64_t n, int64_t M, const int64_t* row_ptr, const int3
              (long long)T, DLP_MAX_T);
     return 9;
   }
-  if (row_ptr[0] != 0 || row_ptr[n] != M) {
-    snprintf(msg, cap, "row pointers run from %lld to %lld, expected 0 to M=%lld", (long long)row_ptr[0], (long long)row_ptr[n], (long long)M);
-    return 2;
-  }
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t e0 = row_ptr[i], e1 = row_ptr[i + 1];
-    if (e1 < e0 || e1 > M) {
-      snprintf(msg, cap, "row pointers of vertex %lld are not ascending within [0, M]", (long long)i);
-      return 2;
-    }
-    for (int64_t e = e0; e < e1; ++e) {
-      if (col[e] < 0 || col[e] >= n) {
-        snprintf(msg, cap, "column index %d of entry %lld out of range", col[e], (long long)e);
-        return 3;
-      }
-      if (e > e0 && col[e - 1] >= col[e]) {
-        snprintf(msg, cap, "row %lld is not canonical: its columns are not strictly ascending (entry %lld)", (long long)i, (long long)e);
-        return 4;
-      }
-      if (!std::isfinite(P[e])) {
-        snprintf(msg, cap, "value %g of entry %lld is not finite", P[e], (long long)e);
-        return 5;
-      }
-    }
-  }
-  for (int64_t q = 0; q < m; ++q)
-    if (ind[q] < 0 || ind[q] >= n) {
-      snprintf(msg, cap, "training vertex %d out of range", ind[q]);
-      return 6;
-    }
-  return 0;
+  const int bad = csr_walk(n, M, row_ptr, col, 2, 3, 4, msg, cap, [&](int64_t, int64_t e) {
+    if (std::isfinite(P[e])) return 0;
+    snprintf(msg, cap, "value %g of entry %lld is not finite", P[e], (long long)e);
+    return 5;
+  });
+  return bad ? bad : csr_check_vertices(ind, m, n, 6, "training", msg, cap);
 }
 
 inline void dlp_make_plan(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* P, int k, int64_t m,
@@ -123,10 +92,9 @@ inline void dlp_make_plan(int64_t n, int64_t M, const int64_t* row_ptr, const in
       D.tcol[q] = (int32_t)i;
       D.tval[q] = P[e];
     }
-  D.lab.assign((size_t)n, -1);
-  for (int64_t q = 0; q < m; ++q) D.lab[ind[q]] = (int32_t)q;
+  D.lab = csr_label_rows(n, m, ind);
   D.P = fs_partials(n);
-  dlp_tiles(k, &D.ntiles, &D.ct);
+  col_tiles(k, DLP_TILE, &D.ntiles, &D.ct);
   D.work = (2 * T + 2) * n * k;
   D.sparse = T * T + (T > 2 ? T - 2 : 0);
   D.grams = T * (T - 1) / 2;

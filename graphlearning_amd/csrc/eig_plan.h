@@ -17,6 +17,7 @@
 // The rotation V[:, :keep] <- V[:, :rows] Y adds, per element, the products V[i, c] * Y[c, q] over c = 0 .. rows - 1 in ascending
 // order from +0.0; then V[:, keep] <- V[:, rows].
 #pragma once
+#include "csr_plan.h"
 #include "fixed_sum.h"
 #include <cmath>
 #include <cstddef>
@@ -43,8 +44,8 @@ inline int64_t eig_device_bytes(int64_t n, int64_t nnz, int64_t m) {
   return (m + 1 + 2) * n * 8 + (n + 1) * 8 + nnz * 12 + fs_partials(n) * (m + 1) * 8 + (int64_t)EIG_MAX_M * EIG_MAX_M * 8 + 8 * (m + 1) * 8;
 }
 
-// 0, or a message in `msg` and: 1 sizes, 2 row pointers, 3 a column index out of range, 4 a row that is not canonical, 6 a value
-// that is not finite, 8 m outside [1, min(n, EIG_MAX_M)]
+// 0, or a message in `msg` and: 1 sizes, 2 row pointers, 3 a column index out of range, 4 a row with columns not strictly ascending,
+// 6 a value that is not finite, 8 m outside [1, min(n, EIG_MAX_M)]
 inline int eig_validate(int64_t n, const int64_t* row_ptr, const int32_t* col, const double* val, int64_t m, char* msg, size_t cap) {
   if (n < 1 || n > 0x7fffffffll) {
     snprintf(msg, cap, "bad size n=%lld (1 .. 2^31 - 1)", (long long)n);
@@ -59,28 +60,11 @@ inline int eig_validate(int64_t n, const int64_t* row_ptr, const int32_t* col, c
     snprintf(msg, cap, "row pointers run from %lld to %lld, expected 0 to at most 2^31 - 1", (long long)row_ptr[0], (long long)M);
     return 2;
   }
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t e0 = row_ptr[i], e1 = row_ptr[i + 1];
-    if (e1 < e0 || e1 > M) {
-      snprintf(msg, cap, "row pointers of vertex %lld are not ascending within [0, nnz]", (long long)i);
-      return 2;
-    }
-    for (int64_t e = e0; e < e1; ++e) {
-      if (col[e] < 0 || col[e] >= n) {
-        snprintf(msg, cap, "column index %d of entry %lld out of range", col[e], (long long)e);
-        return 3;
-      }
-      if (e > e0 && col[e - 1] >= col[e]) {
-        snprintf(msg, cap, "row %lld is not canonical: its columns are not strictly ascending (entry %lld)", (long long)i, (long long)e);
-        return 4;
-      }
-      if (!std::isfinite(val[e])) {
-        snprintf(msg, cap, "value %g of entry %lld is not finite", val[e], (long long)e);
-        return 6;
-      }
-    }
-  }
-  return 0;
+  return csr_walk(n, M, row_ptr, col, 2, 3, 4, msg, cap, [&](int64_t, int64_t e) {
+    if (std::isfinite(val[e])) return 0;
+    snprintf(msg, cap, "value %g of entry %lld is not finite", val[e], (long long)e);
+    return 6;
+  });
 }
 
 // ---- the documented order on the host: what the device must equal bit for bit ------------------------------------------------------

@@ -24,6 +24,7 @@
 //
 // Caps: k <= 256, m <= 256, k * m <= MMBO_CAP = 4096 (Z in LDS: 32 KiB and a pad), n * m, T * n and partials * k * m at most 2^31.
 #pragma once
+#include "csr_plan.h"
 #include "fixed_sum.h"
 #include <cmath>
 #include <cstddef>
@@ -85,10 +86,7 @@ inline int mmbo_validate(int64_t n, int m, const double* X, const double* vals, 
     return 8;
   }
   for (int64_t q = 0; q < ntrain; ++q) {
-    if (ind[q] < 0 || ind[q] >= n) {
-      snprintf(msg, cap, "training vertex %d out of range", ind[q]);
-      return 4;
-    }
+    if (const int bad = csr_check_vertex(ind[q], n, 4, "training", msg, cap)) return bad;
     if (lab[q] < 0 || lab[q] >= k) {
       snprintf(msg, cap, "training label %d outside [0, %d)", lab[q], k);
       return 5;

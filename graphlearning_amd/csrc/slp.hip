@@ -106,7 +106,7 @@ extern "C" int glx_slp_iterate(int64_t n, int64_t M, const int64_t* row_ptr, con
   GLX_CHECK(n * (int64_t)C <= (1ll << 40) / 8, GLX_EUNSUPPORTED, "glx_slp_iterate: a result of n * C = %lld values", (long long)(n * (int64_t)C));
   std::vector<int32_t> rev((size_t)M);
   slp_reverse_index(n, row_ptr, col, rev.data());
-  const std::vector<int32_t> lab = slp_label_rows(n, m, ind);
+  const std::vector<int32_t> lab = csr_label_rows(n, m, ind);
   const std::vector<SlpTile> tiles = slp_tiles(C);
   const int cpad_max = tiles[0].cpad;               // the first tile is the widest
 

@@ -11,8 +11,9 @@
 // The column tiling.  The state is stored class columns contiguous: Y (M, cpad), u and ut (n, cpad), so that a gathered record
 // Y[rev[e]] or ut[j] is one 128-byte line for up to 16 columns (cpad: the tile's columns rounded up to 1, 2, 4, 8 or 16 doubles, a
 // record never straddles a line).  More than SLP_TILE columns run tile after tile, each tile a complete solve of its columns -- the
-// columns are independent, so the result does not depend on the tiling --, the tiles' widths within one column of each other.
+// columns are independent, so the result does not depend on the tiling --, by the tile rule of csr_plan.h.
 #pragma once
+#include "csr_plan.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -30,15 +31,13 @@ struct SlpTile {
 inline std::vector<SlpTile> slp_tiles(int C) {
   std::vector<SlpTile> t;
   if (C < 1) return t;
-  const int nt = (C + SLP_TILE - 1) / SLP_TILE;
-  const int base = C / nt, extra = C % nt;              // the first `extra` tiles hold one column more
-  int c0 = 0;
+  int nt, ct;
+  col_tiles(C, SLP_TILE, &nt, &ct);
   for (int q = 0; q < nt; ++q) {
-    const int cols = base + (q < extra ? 1 : 0);
-    int cpad = 1;
+    int c0, cols, cpad = 1;
+    col_tile(C, SLP_TILE, q, &c0, &cols);
     while (cpad < cols) cpad *= 2;
     t.push_back({(int32_t)c0, (int32_t)cols, (int32_t)cpad});
-    c0 += cols;
   }
   return t;
 }
@@ -52,49 +51,30 @@ inline int slp_validate(int64_t n, int64_t M, const int64_t* row_ptr, const int3
     snprintf(msg, cap, "bad sizes (n=%lld M=%lld m=%lld C=%d; n and M at most 2^31 - 1)", (long long)n, (long long)M, (long long)m, C);
     return 1;
   }
-  if (row_ptr[0] != 0 || row_ptr[n] != M) {
-    snprintf(msg, cap, "row pointers run from %lld to %lld, expected 0 to M=%lld", (long long)row_ptr[0], (long long)row_ptr[n], (long long)M);
-    return 2;
-  }
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t e0 = row_ptr[i], e1 = row_ptr[i + 1];
-    if (e1 < e0 || e1 > M) {
-      snprintf(msg, cap, "row pointers of vertex %lld are not ascending within [0, M]", (long long)i);
-      return 2;
-    }
-    if (e1 == e0) {
-      snprintf(msg, cap, "vertex %lld has no stored entry (its degree is zero: the update divides by it)", (long long)i);
-      return 3;
-    }
-    for (int64_t e = e0; e < e1; ++e) {
-      if (col[e] < 0 || col[e] >= n) {
-        snprintf(msg, cap, "column index %d of entry %lld out of range", col[e], (long long)e);
-        return 4;
-      }
-      if (e > e0 && col[e - 1] >= col[e]) {
-        snprintf(msg, cap, "row %lld is not canonical: its columns are not strictly ascending (entry %lld)", (long long)i, (long long)e);
-        return 5;
-      }
-      if (!(std::isfinite(W[e]) && W[e] > 0)) {
-        snprintf(msg, cap, "weight %g of entry %lld is not finite and > 0", W[e], (long long)e);
-        return 6;
-      }
-      if (!std::isfinite(lam[e])) {
-        snprintf(msg, cap, "lam %g of entry %lld is not finite", lam[e], (long long)e);
+  const int bad = csr_walk(
+      n, M, row_ptr, col, 2, 4, 5, msg, cap,
+      [&](int64_t i, int64_t count) {
+        if (count > 0) return 0;
+        snprintf(msg, cap, "vertex %lld has no stored entry (its degree is zero: the update divides by it)", (long long)i);
+        return 3;
+      },
+      [&](int64_t, int64_t e) {
+        if (!(std::isfinite(W[e]) && W[e] > 0)) {
+          snprintf(msg, cap, "weight %g of entry %lld is not finite and > 0", W[e], (long long)e);
+          return 6;
+        }
+        if (!std::isfinite(lam[e])) {
+          snprintf(msg, cap, "lam %g of entry %lld is not finite", lam[e], (long long)e);
+          return 7;
+        }
+        return 0;
+      },
+      [&](int64_t i) {
+        if (std::isfinite(gamma[i])) return 0;
+        snprintf(msg, cap, "gamma %g of vertex %lld is not finite", gamma[i], (long long)i);
         return 7;
-      }
-    }
-    if (!std::isfinite(gamma[i])) {
-      snprintf(msg, cap, "gamma %g of vertex %lld is not finite", gamma[i], (long long)i);
-      return 7;
-    }
-  }
-  for (int64_t q = 0; q < m; ++q)
-    if (ind[q] < 0 || ind[q] >= n) {
-      snprintf(msg, cap, "labelled vertex %d out of range", ind[q]);
-      return 8;
-    }
-  return 0;
+      });
+  return bad ? bad : csr_check_vertices(ind, m, n, 8, "labelled", msg, cap);
 }
 
 // rev[e] for every entry of a canonical W (validated: slp_validate); M <= 2^31 - 1
@@ -110,12 +90,7 @@ inline void slp_reverse_index(int64_t n, const int64_t* row_ptr, const int32_t* 
     }
 }
 
-// lab[i] = the row of `val` vertex i takes, -1 where it is not labelled; a vertex listed twice takes its last row
-inline std::vector<int32_t> slp_label_rows(int64_t n, int64_t m, const int32_t* ind) {
-  std::vector<int32_t> lab((size_t)n, -1);
-  for (int64_t q = 0; q < m; ++q) lab[ind[q]] = (int32_t)q;
-  return lab;
-}
+inline std::vector<int32_t> slp_label_rows(int64_t n, int64_t m, const int32_t* ind) { return csr_label_rows(n, m, ind); }
 
 // The contract on the host, one column after another, entry by entry (compiled with -ffp-contract=off): what the device must equal.
 inline void slp_host_reference(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* col, const double* W, const double* lam,

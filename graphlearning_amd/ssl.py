@@ -1320,6 +1320,44 @@ class plaplace(ssl):
         return self._solve(train_ind, vals)
 
 
+def _training_set(name, n, train_ind, train_labels, max_classes=None, cap_text='%d columns per call'):
+    """The training set of a one-call learner `name` on n vertices: (train_ind, train_labels, k), both raveled.  ValueError, in this
+    order: arrays of different lengths, an empty set, an index out of range or not an integer, labels that are not exactly 0 .. k-1,
+    more than max_classes classes (cap_text words the cap)."""
+    train_ind = np.asarray(train_ind).ravel()
+    train_labels = np.asarray(train_labels).ravel()
+    if len(train_ind) != len(train_labels):
+        raise ValueError('%s: %d training indices for %d labels' % (name, len(train_ind), len(train_labels)))
+    if len(train_ind) == 0:
+        raise ValueError('%s: no training vertex' % name)
+    if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
+        raise ValueError('%s: train_ind out of range (or not an integer array)' % name)
+    classes = np.unique(train_labels)
+    k = len(classes)
+    if not np.array_equal(classes, np.arange(k)):
+        raise ValueError('%s: the labels are not exactly 0 .. %d' % (name, k - 1))
+    if max_classes is not None and k > max_classes:
+        raise ValueError(('%s: %d classes, at most ' + cap_text) % (name, k, max_classes))
+    return train_ind, train_labels, k
+
+
+def _canonical_weights(W, drop_diagonal=False):
+    """A float64 CSR copy of the weight matrix in canonical form -- duplicates summed, stored zeros removed, columns ascending --,
+    without its diagonal on request.  What a value may be is the learner's own rule."""
+    if drop_diagonal:
+        W = W - sparse.spdiags(W.diagonal(), 0, W.shape[0], W.shape[0])      # the diagonal goes as in the reference
+    W = sparse.csr_matrix(W, dtype=np.float64, copy=not drop_diagonal)
+    W.sum_duplicates()
+    W.eliminate_zeros()
+    W.sort_indices()
+    return W
+
+
+def _onehot(labels, k):
+    """(len(labels), k) float64: 1.0 at [q, labels[q]], 0.0 elsewhere"""
+    return (labels.astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
+
+
 SLP_HISTORY_BYTES = 1 << 30       # sparse_label_propagation with all_labels: the iterates (T, n, k) the device call hands back, at most
 
 
@@ -1340,13 +1378,10 @@ class sparse_label_propagation(ssl):
     def _operands(self):
         """The canonical CSR arrays of the weight matrix with lam per entry and gamma per vertex (host numpy: the reference's own
         element-wise calls), rebuilt in every fit as the reference does."""
-        W = sparse.csr_matrix(self.graph.weight_matrix, dtype=np.float64, copy=True)
-        W.sum_duplicates()
+        W = _canonical_weights(self.graph.weight_matrix)
         bad = ~(np.isfinite(W.data) & (W.data >= 0))
         if bad.any():
             raise ValueError('sparse_label_propagation: weight %r is negative, NaN or infinite' % (W.data[bad][0],))
-        W.eliminate_zeros()
-        W.sort_indices()
         if not np.all(W.data > 0):
             raise ValueError('sparse_label_propagation: a weight is zero after eliminate_zeros')
         empty = np.where(np.diff(W.indptr) == 0)[0]
@@ -1363,25 +1398,13 @@ class sparse_label_propagation(ssl):
     def _fit(self, train_ind, train_labels, all_labels=None):
         n = self.graph.num_nodes
         T = max(int(self.T), 0)
-        train_ind = np.asarray(train_ind).ravel()
-        train_labels = np.asarray(train_labels).ravel()
-        if len(train_ind) != len(train_labels):
-            raise ValueError('sparse_label_propagation: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
-        if len(train_ind) == 0:
-            raise ValueError('sparse_label_propagation: no training vertex')
-        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
-            raise ValueError('sparse_label_propagation: train_ind out of range (or not an integer array)')
-        classes = np.unique(train_labels)
-        k = len(classes)
-        if not np.array_equal(classes, np.arange(k)):
-            raise ValueError('sparse_label_propagation: the labels are not exactly 0 .. %d' % (k - 1))
+        train_ind, train_labels, k = _training_set('sparse_label_propagation', n, train_ind, train_labels)
         want_hist = all_labels is not None and T > 0
         if want_hist and T * n * k * 8 > SLP_HISTORY_BYTES:
             raise ValueError('sparse_label_propagation: the iterates of an all_labels fit take %d bytes (T=%d x n=%d x k=%d doubles), '
                              'above the limit of %d' % (T * n * k * 8, T, n, k, SLP_HISTORY_BYTES))
         row_ptr, col, w, lam, gamma = self._operands()
-        val = (train_labels.astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
-        u, hist, plan = _hip.slp_iterate(row_ptr, col, w, lam, gamma, train_ind.astype(np.int32), val, T, device=self.device,
+        u, hist, plan = _hip.slp_iterate(row_ptr, col, w, lam, gamma, train_ind.astype(np.int32), _onehot(train_labels, k), T, device=self.device,
                                          want_history=want_hist)
         self.num_iter = T
         self.slp_plan = plan
@@ -1419,31 +1442,14 @@ class centered_kernel(ssl):
 
     def _fit(self, train_ind, train_labels, all_labels=None):
         n = self.graph.num_nodes
-        train_ind = np.asarray(train_ind).ravel()
-        train_labels = np.asarray(train_labels).ravel()
         if not int(self.power_it) >= 1:
             raise ValueError('centered_kernel: power_it=%r, at least one power iteration is needed' % (self.power_it,))
-        if len(train_ind) != len(train_labels):
-            raise ValueError('centered_kernel: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
-        if len(train_ind) == 0:
-            raise ValueError('centered_kernel: no training vertex')
-        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
-            raise ValueError('centered_kernel: train_ind out of range (or not an integer array)')
-        classes = np.unique(train_labels)
-        k = len(classes)
-        if not np.array_equal(classes, np.arange(k)):
-            raise ValueError('centered_kernel: the labels are not exactly 0 .. %d' % (k - 1))
-        if k > 256:
-            raise ValueError('centered_kernel: %d classes, at most 256 columns per call' % k)
-        W = self.graph.weight_matrix
-        W = sparse.csr_matrix(W - sparse.spdiags(W.diagonal(), 0, n, n), dtype=np.float64)      # the diagonal goes as in the reference
-        W.sum_duplicates()
-        W.eliminate_zeros()
-        W.sort_indices()
+        train_ind, train_labels, k = _training_set('centered_kernel', n, train_ind, train_labels, max_classes=256)
+        W = _canonical_weights(self.graph.weight_matrix, drop_diagonal=True)
         if not np.all(np.isfinite(W.data)):
             raise ValueError('centered_kernel: a weight is NaN or infinite')
         K = np.zeros((n, k))
-        K[train_ind] = (train_labels.astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
+        K[train_ind] = _onehot(train_labels, k)
         K[train_ind, :] -= np.sum(K, axis=0) / len(train_ind)
         # rows listed twice: the device call gives a vertex its last row, as the assignment above does
         val = np.ascontiguousarray(K[train_ind])
@@ -1494,26 +1500,13 @@ class dynamic_label_propagation(ssl):
 
     def _fit(self, train_ind, train_labels, all_labels=None):
         n = self.graph.num_nodes
-        train_ind = np.asarray(train_ind).ravel()
-        train_labels = np.asarray(train_labels).ravel()
         T = self.T
         if not (T == int(T) and 1 <= int(T) <= DLP_MAX_T):
             raise ValueError('dynamic_label_propagation: T=%r must be a whole number from 1 to %d' % (T, DLP_MAX_T))
         T = int(T)
         if not (np.isfinite(self.alpha) and np.isfinite(self.lam)):
             raise ValueError('dynamic_label_propagation: alpha=%r or lam=%r is not finite' % (self.alpha, self.lam))
-        if len(train_ind) != len(train_labels):
-            raise ValueError('dynamic_label_propagation: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
-        if len(train_ind) == 0:
-            raise ValueError('dynamic_label_propagation: no training vertex')
-        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
-            raise ValueError('dynamic_label_propagation: train_ind out of range (or not an integer array)')
-        classes = np.unique(train_labels)
-        k = len(classes)
-        if not np.array_equal(classes, np.arange(k)):
-            raise ValueError('dynamic_label_propagation: the labels are not exactly 0 .. %d' % (k - 1))
-        if k > DLP_MAX_CLASSES:
-            raise ValueError('dynamic_label_propagation: %d classes, at most %d columns per call' % (k, DLP_MAX_CLASSES))
+        train_ind, train_labels, k = _training_set('dynamic_label_propagation', n, train_ind, train_labels, max_classes=DLP_MAX_CLASSES)
         if (2 * T + 2) * n * k > DLP_MAX_WORK:
             raise ValueError('dynamic_label_propagation: (2 T + 2) n k = %d values of workspace (T=%d, n=%d, k=%d), above the limit of %d'
                              % ((2 * T + 2) * n * k, T, n, k, DLP_MAX_WORK))
@@ -1521,11 +1514,7 @@ class dynamic_label_propagation(ssl):
         if want_hist and T * n * k * 8 > DLP_HISTORY_BYTES:
             raise ValueError('dynamic_label_propagation: the iterates of an all_labels fit take %d bytes (T=%d x n=%d x k=%d doubles), '
                              'above the limit of %d' % (T * n * k * 8, T, n, k, DLP_HISTORY_BYTES))
-        W = self.graph.weight_matrix
-        W = sparse.csr_matrix(W - sparse.spdiags(W.diagonal(), 0, n, n), dtype=np.float64)      # the diagonal goes as in the reference
-        W.sum_duplicates()
-        W.eliminate_zeros()
-        W.sort_indices()
+        W = _canonical_weights(self.graph.weight_matrix, drop_diagonal=True)
         if not np.all(np.isfinite(W.data)):
             raise ValueError('dynamic_label_propagation: a weight is NaN or infinite')
         G = graph_mod.graph(W)
@@ -1542,7 +1531,7 @@ class dynamic_label_propagation(ssl):
         if not np.all(np.isfinite(P.data)):
             raise ValueError('dynamic_label_propagation: an entry of P = D^-1 W is not finite')
         # rows listed twice: the device call gives a vertex its last row, as the reference's assignment u[train_ind, :] = K does
-        val = (train_labels.astype(np.int64)[:, None] == np.arange(k)[None, :]).astype(np.float64)
+        val = _onehot(train_labels, k)
         u, hist, plan = _hip.dlp_solve(P.indptr.astype(np.int64), P.indices.astype(np.int32), P.data, train_ind.astype(np.int32), val,
                                        alpha=float(self.alpha), lam=float(self.lam), T=T, device=self.device, want_history=want_hist)
         self.num_iter = T
@@ -1592,26 +1581,13 @@ class multiclass_mbo(ssl):
 
     def _fit(self, train_ind, train_labels, all_labels=None):
         n = self.graph.num_nodes
-        train_ind = np.asarray(train_ind).ravel()
-        train_labels = np.asarray(train_labels).ravel()
         Ns, T = self.Ns, self.T
         if not (Ns == int(Ns) and T == int(T) and int(Ns) >= 1 and int(T) >= 1 and int(T) * int(Ns) <= 1 << 24):
             raise ValueError('multiclass_mbo: Ns=%r and T=%r must be whole numbers, at least 1, with T * Ns at most 2^24' % (Ns, T))
         Ns, T = int(Ns), int(T)
         if not (np.isfinite(self.dt) and np.isfinite(self.mu)):
             raise ValueError('multiclass_mbo: dt=%r or mu=%r is not finite' % (self.dt, self.mu))
-        if len(train_ind) != len(train_labels):
-            raise ValueError('multiclass_mbo: %d training indices for %d labels' % (len(train_ind), len(train_labels)))
-        if len(train_ind) == 0:
-            raise ValueError('multiclass_mbo: no training vertex')
-        if train_ind.dtype.kind not in 'iu' or train_ind.min() < 0 or train_ind.max() >= n:
-            raise ValueError('multiclass_mbo: train_ind out of range (or not an integer array)')
-        classes = np.unique(train_labels)
-        k = len(classes)
-        if not np.array_equal(classes, np.arange(k)):
-            raise ValueError('multiclass_mbo: the labels are not exactly 0 .. %d' % (k - 1))
-        if k > 256:
-            raise ValueError('multiclass_mbo: %d classes, at most 256 per call' % k)
+        train_ind, train_labels, k = _training_set('multiclass_mbo', n, train_ind, train_labels, max_classes=256, cap_text='%d per call')
         if k * int(self.num_eig) > MMBO_CAP:
             raise ValueError('multiclass_mbo: %d classes times num_eig=%d is above the limit of %d' % (k, int(self.num_eig), MMBO_CAP))
         vals, X = self.graph.eigen_decomp(normalization='normalized', k=self.num_eig)

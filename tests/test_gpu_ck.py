@@ -101,6 +101,29 @@ def test_seeded_shapes_bit_for_bit(gl, seed, n, k, hub, directed, lonely):
     assert plan[0] == 2 and plan[1] == 2 * 100 + 2 + 2 * 64 * ((T + 63) // 64) and plan[3] == (n + 63) // 64
 
 
+# seed, n, k: uneven column tiles together with a ragged last row block, the smallest shapes at which a wrong first column or width of
+# a tile shows: k = 1 and 16 are one tile, 17 is 9 + 8, 33 is three tiles of 11; n = 65 and 130 leave the 64 rows of a partial with a
+# remainder of one row and of two ((65, 17) is among SHAPES); the seeds are ones whose problem stops within 220 iterations at tol = 1e-6
+TILE_SHAPES = [(205, 65, 1), (202, 65, 16), (202, 65, 33), (208, 130, 1), (200, 130, 16), (200, 130, 17), (200, 130, 33)]
+
+
+@pytest.fixture(scope='module')
+def host_lib(tmp_path_factory):
+    return ref.build_host_lib(tmp_path_factory.mktemp('ck_plan'))
+
+
+@pytest.mark.parametrize('seed,n,k', TILE_SHAPES)
+def test_uneven_tiles_on_a_ragged_row_block_bit_for_bit(gl, host_lib, seed, n, k):
+    """the device against ck_host_reference (csrc/ck_plan.h built on the host)"""
+    W, ind, val, e = ref.random_problem(seed, n, k)
+    want_u, want_l, want_T, want_errs, capped = ref.host_solve(host_lib, W.indptr, W.indices, W.data, ind, val, e, tol=1e-6, cap=256)
+    assert not capped and want_T <= 220 and np.all(np.isfinite(want_u))
+    u, l, T, errs, plan = solve(W, ind, val, e, tol=1e-6, err_cap=want_T)
+    print((n, k), 'T', T, want_T, 'differing values', int((u != want_u).sum()), 'plan', plan)
+    assert T == want_T and same_bits(u, want_u) and l == want_l and same_bits(errs, want_errs)
+    assert plan[3] == (n + 63) // 64
+
+
 # hub row length -> a seed whose problem stops within a few hundred iterations
 HUB_SEEDS = {63: 105, 64: 43, 65: 40, 255: 41, 256: 102, 257: 41}
 

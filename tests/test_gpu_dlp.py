@@ -83,6 +83,20 @@ def test_seeded_shapes_bit_for_bit(gl, lib, n, k, T, options):
     assert same_bits(u[ind], val) and same_bits(hist[-1], u)
 
 
+# n, k: uneven column tiles together with a ragged last row block, the smallest shapes at which a wrong first column or width of a tile
+# shows in the sparse pass or the Gram pass: k = 1 and 16 are one tile, 17 is 9 + 8, 33 is three tiles of 11; n = 65 and 130 leave the 64
+# rows of a partial with a remainder of one row and of two ((65, 17) is among SHAPES).  T = 3: three Grams, an epilogue with and without
+# the reset of the training rows
+TILE_SHAPES = [(65, 1), (65, 16), (65, 33), (130, 1), (130, 16), (130, 17), (130, 33)]
+
+
+@pytest.mark.parametrize('n,k', TILE_SHAPES)
+def test_uneven_tiles_on_a_ragged_row_block_bit_for_bit(gl, lib, n, k):
+    P, ind, val = ref.random_problem(n + k, n, k)
+    u, hist = check_against_host(lib, P, ind, val, T=3)
+    assert same_bits(u[ind], val) and same_bits(hist[-1], u)
+
+
 def test_the_directed_golden_graph_bit_for_bit(gl, gold, lib):
     W, truth, ind, labels, k, params = golden_case(gold, 'directed_T3')
     P = ref.transition(W)
