@@ -19,6 +19,7 @@ from . import trainsets
 from . import weightmatrix
 from . import ssl
 from . import clustering
+from . import active_learning
 from ._hip import GlxError
 
 __version__ = '0.1.0'

@@ -181,6 +181,13 @@ _SIGNATURES = {
     'glx_incres_stats': [_vp, _i64p],
     'glx_incres_destroy': [_vp],
     'glx_host_group_by_label': [C.c_int64, _vp, C.c_int, _vp, _vp],
+    'glx_acq_create': [C.c_int64, C.c_int, _vp, _vp, C.c_double, C.c_int, C.POINTER(_vp)],
+    'glx_acq_compute': [_vp, C.c_int, _vp, C.c_int64, _vp, _vp],
+    'glx_acq_update': [_vp, _vp, C.c_int64],
+    'glx_acq_greedy': [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp],
+    'glx_acq_get_c': [_vp, _vp],
+    'glx_acq_stats': [_vp, _i64p],
+    'glx_acq_destroy': [_vp],
     'glx_exp_cr': [_vp, _vp, C.c_int64, C.c_int],
     'glx_argmax_project': [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
     'glx_argmax_project_t': [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _f64p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int],
@@ -1485,6 +1492,84 @@ class Incres:
             lib = load(required=False)
             if lib is not None:
                 lib.glx_incres_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ACQ_VAR, ACQ_SIGMA, ACQ_MC, ACQ_MCVAR = 0, 1, 2, 3          # the kinds of glx_acq_compute (include/glx_experimental.h)
+ACQ_MAX_M = 256
+
+
+class Acq:
+    """The device half of the acquisition functions of active learning (glx_acq_*, csrc/acq.hip; the contract is DESIGN.md 4.19): the
+    eigenvectors V (n, M) and the covariance C (M, M) stay on the device.  compute(kind, cand, unc) evaluates the candidates,
+    update(query) applies the rank-one steps of a batch in one launch, greedy(kind, cand, b) returns the positions in cand and the
+    values that b rounds of evaluate / take the first maximum / update choose, on a scratch copy of C.  A context manager; close()
+    releases the device memory.  GlxError on every refusal of the library; the object stays usable after it."""
+
+    def __init__(self, V, C_, gamma2, device=None):
+        self._h = _vp()
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        C_ = np.ascontiguousarray(C_, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] < 1 or C_.shape != (V.shape[1], V.shape[1]):
+            raise GlxError('Acq: V of shape %s and C of shape %s, expected (n, M) and (M, M)' % (V.shape, C_.shape))
+        self.n, self.M = V.shape
+        check(load().glx_acq_create(self.n, self.M, _ptr(V), _ptr(C_), float(gamma2), _dev(device), C.byref(self._h)), 'glx_acq_create')
+
+    def _handle(self):
+        if not self._h.value:
+            raise GlxError('Acq: the object is closed')
+        return self._h
+
+    def compute(self, kind, cand, unc=None):
+        cand = np.ascontiguousarray(cand, dtype=np.int32).ravel()
+        if unc is not None:
+            unc = _dense(np.asarray(unc).ravel(), np.float64, (len(cand),), 'unc')
+        vals = np.empty(len(cand), dtype=np.float64)
+        check(load().glx_acq_compute(self._handle(), int(kind), _ptr(cand), len(cand), _ptr(unc), _ptr(vals)), 'glx_acq_compute')
+        return vals
+
+    def update(self, query):
+        query = np.ascontiguousarray(query, dtype=np.int32).ravel()
+        check(load().glx_acq_update(self._handle(), _ptr(query), len(query)), 'glx_acq_update')
+
+    def greedy(self, kind, cand, b):
+        """(positions in cand (b) int32, their values (b))"""
+        cand = np.ascontiguousarray(cand, dtype=np.int32).ravel()
+        b = int(b)
+        queries = np.empty(max(b, 1), dtype=np.int32)
+        vals = np.empty(max(b, 1), dtype=np.float64)
+        check(load().glx_acq_greedy(self._handle(), int(kind), _ptr(cand), len(cand), b, _ptr(queries), _ptr(vals)), 'glx_acq_greedy')
+        return queries[:b], vals[:b]
+
+    def get_c(self):
+        out = np.empty((self.M, self.M), dtype=np.float64)
+        check(load().glx_acq_get_c(self._handle(), _ptr(out)), 'glx_acq_get_c')
+        return out
+
+    def stats(self):
+        """dict: pass_launches, update_launches, greedy_launches, tile_rows, pass_lds, update_lds, n, M"""
+        out = (C.c_int64 * 8)()
+        check(load().glx_acq_stats(self._handle(), out), 'glx_acq_stats')
+        names = ('pass_launches', 'update_launches', 'greedy_launches', 'tile_rows', 'pass_lds', 'update_lds', 'n', 'M')
+        return dict(zip(names, (int(v) for v in out)))
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            lib = load(required=False)
+            if lib is not None:
+                lib.glx_acq_destroy(self._h)
             self._h = _vp()
 
     def __enter__(self):

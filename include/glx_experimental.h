@@ -383,6 +383,42 @@ int glx_dlp_solve(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* c
                   const int32_t* ind, const double* val, double alpha, double lam, int64_t T, double* u, double* hist,
                   int64_t* plan_out, int device);
 
+/* ---- acquisition functions of active learning: graphlearning_amd.active_learning (csrc/acq.hip, csrc/acq_plan.h) ------------------
+ * var_opt, sigma_opt, model_change and model_change_var_opt of the reference (active_learning.py:237-575) in the truncated eigenbasis.
+ * The handle keeps V (n, M) row-major -- vertex i is the row v_i -- and the covariance C (M, M) row-major on the device; gamma2 is fixed
+ * at creation.  The order of every sum and operation is that of DESIGN.md 4.19 (chains in ascending index, no fused multiply-add, no
+ * floating-point atomics), so every result is a pure function of the arguments and equals acq_host_compute / acq_host_update /
+ * acq_host_greedy of csrc/acq_plan.h bit for bit.  OWNERSHIP: the caller owns *out and releases it with glx_acq_destroy.  All pointers
+ * are host pointers; every call returns with its work complete.
+ * glx_acq_compute: vals_out (nc) <- the value of `kind` at the rows cand[0 .. nc) of V (positions may repeat, in any order; nc = 0
+ *   launches nothing), with w = C v, d = v.w: VAR (sqrt(sum w^2))^2 / (gamma2 + d); SIGMA (sum w)^2 / (gamma2 + d); MC unc sqrt(sum w^2)
+ *   / (gamma2 + d); MCVAR unc (sqrt(sum w^2))^2 / (gamma2 + d).  unc (nc): the multiplier of MC and MCVAR (required there, ignored
+ *   otherwise).  Values that are not finite are returned as they are.
+ * glx_acq_update: for each query in order w = C v, ip = v.w, C[a, b] <- C[a, b] - (w[a] w[b]) / (gamma2 + ip): numpy's
+ *   C -= np.outer(w, w) / (gamma2 + ip).  One launch for the batch; repeated indices are legal.
+ * glx_acq_greedy (VAR and SIGMA): b rounds on a scratch copy of C -- evaluate, take the first maximum (equal values go to the smallest
+ *   position in cand), strike the chosen vertex from the candidates, apply its rank-one step.  queries_out (b) <- the chosen POSITIONS
+ *   in cand, vals_out (b) <- their values.  The handle's C is left as it was; nothing is read back between the rounds.
+ * glx_acq_get_c: C_out (M, M) <- the current covariance.
+ * glx_acq_stats: out[8] <- launches of the pass by glx_acq_compute, of the update, of the greedy design (two per round), candidates per
+ *   workgroup of the pass, bytes of LDS of the pass, bytes of LDS of the update (0: C stays in L2 between the queries), n, M.
+ * GLX_EINVAL: a null argument, n or M below 1, an entry of V or C or gamma2 not finite, a kind outside the table (for the greedy design
+ *   outside VAR and SIGMA), a position outside [0, n), MC or MCVAR without unc, b above the number of distinct vertices in cand, a
+ *   greedy round whose maximum is not finite (the message names the round; the outputs hold the rounds before it).
+ * GLX_EUNSUPPORTED: M > 256, n > 2^31 - 1. */
+#define GLX_ACQ_VAR 0
+#define GLX_ACQ_SIGMA 1
+#define GLX_ACQ_MC 2
+#define GLX_ACQ_MCVAR 3
+typedef struct glx_acq glx_acq;
+int glx_acq_create(int64_t n, int M, const double* V, const double* C, double gamma2, int device, glx_acq** out);
+int glx_acq_compute(glx_acq* h, int kind, const int32_t* cand, int64_t nc, const double* unc, double* vals_out);
+int glx_acq_update(glx_acq* h, const int32_t* query, int64_t nq);
+int glx_acq_greedy(glx_acq* h, int kind, const int32_t* cand, int64_t nc, int64_t b, int32_t* queries_out, double* vals_out);
+int glx_acq_get_c(glx_acq* h, double* C_out);
+int glx_acq_stats(glx_acq* h, int64_t* out);
+int glx_acq_destroy(glx_acq* h);
+
 #ifdef __cplusplus
 }
 #endif
