@@ -378,15 +378,31 @@ def poisson_fit(W, train_ind, train_labels, solver='conjugate_gradient', min_ite
 
 
 # ----------------------------------------------------------------------------
-# a-5  Laplace learning (graphlearning/ssl.py:1206-1261), reweighting='none', order=1
+# a-5  Laplace learning (graphlearning/ssl.py:1206-1261), reweighting='none', any order
+# (tau scalar or vector; the reweighted fits are laplace_reweighted_fit below)
 # ----------------------------------------------------------------------------
-def laplace_system(W, train_ind, train_labels, normalization='combinatorial', tau=0):
+def laplace_operator(W, normalization='combinatorial', tau=0, order=1):
+    """tau + graph Laplacian, raised to `order` as ssl.py:1222-1228 does it: Lpow = L*L, then L*Lpow for every further order
+    (scipy's SpGEMM: the rows of the result come out unsorted, in the order the products reach their columns)."""
+    W = sparse.csr_matrix(W)
+    n = W.shape[0]
+    tau_vec = np.ones(n) * tau if np.isscalar(tau) else np.asarray(tau, dtype=float)
+    L = sparse.spdiags(tau_vec, 0, n, n) + laplacian(W, normalization)
+    if order > 1:
+        Lpow = L * L
+        if order > 2:
+            for i in range(2, order):
+                Lpow = L * Lpow
+        L = Lpow
+    return L
+
+
+def laplace_system(W, train_ind, train_labels, normalization='combinatorial', tau=0, order=1):
     """Dirichlet sub-system of ssl.py:1222-1246: returns (MAM, Mb, Mdiag, idx, F, k)."""
     W = sparse.csr_matrix(W)
     n = W.shape[0]
     k = len(np.unique(train_labels))
-    tau_vec = np.ones(n) * tau if np.isscalar(tau) else np.asarray(tau, dtype=float)
-    L = sparse.spdiags(tau_vec, 0, n, n) + laplacian(W, normalization)
+    L = laplace_operator(W, normalization, tau, order)
     F = labels_to_onehot(train_labels, k)
     idx = np.full((n,), True, dtype=bool)
     idx[train_ind] = False
@@ -401,10 +417,10 @@ def laplace_system(W, train_ind, train_labels, normalization='combinatorial', ta
 
 
 def laplace_fit(W, train_ind, train_labels, normalization='combinatorial', tau=0,
-                mean_shift=False, tol=1e-5, return_iters=False):
+                mean_shift=False, tol=1e-5, return_iters=False, order=1):
     """ssl.laplace._fit, ssl.py:1206-1261."""
     n = W.shape[0]
-    MAM, Mb, M, idx, F, k = laplace_system(W, train_ind, train_labels, normalization, tau)
+    MAM, Mb, M, idx, F, k = laplace_system(W, train_ind, train_labels, normalization, tau, order)
     v, it, err = conjgrad(MAM, Mb, tol=tol, return_iters=True)
     v = M * v
     u = np.zeros((n, k))

@@ -197,3 +197,39 @@ def test_g11_properly(golden):
             Wg = csr_from(g, tag + '_Wr_' + ptag)
             assert np.array_equal(Wr.indices, Wg.indices) and np.array_equal(Wr.data, Wg.data), (tag, ptag)
         assert np.array_equal(orc.laplace_reweighted_fit(W, ti, lab[ti], 'properly', X=X), g[tag + '_laplace_prob']), tag
+
+
+def _g24_graph(g, n):
+    import laplace_order_ref as lo
+    J, D = lo.knn_lists(g, n)
+    return orc.knn_weights(J, D, lo.K)
+
+
+@pytest.mark.parametrize('order', [1, 2, 3])
+def test_g24_laplace_order(order):
+    """ssl.laplace(order=2 | 3) and vector tau (ssl.py:1222-1228): the oracle with `order` reproduces every u the reference recorded,
+    bit for bit -- what lets the GPU tests compare against the oracle at these orders."""
+    import laplace_order_ref as lo
+    g = lo.load_golden()
+    cases = [c for c in lo.CASES if c[1] == order]
+    assert len(cases) == {1: 2, 2: 13, 3: 12}[order]
+    W = {n: _g24_graph(g, n) for n in {c[0] for c in cases}}
+    for case in cases:
+        n, _, norm, tau, ms = case
+        ti, lab = lo.training_set(g, n)
+        u, it = orc.laplace_fit(W[n], ti, lab, normalization=norm, tau=lo.tau_value(g, n, tau), mean_shift=ms, tol=lo.TOL, order=order,
+                                return_iters=True)
+        key = lo.case_key(*case)
+        assert it == int(g['iters_' + key]), key
+        assert np.array_equal(u, g['u_' + key]), key
+
+
+def test_g24_randomwalk_alpha():
+    """ssl.randomwalk(alpha=0.5 | 0.99): the oracle reproduces the reference's u bit for bit."""
+    import laplace_order_ref as lo
+    g = lo.load_golden()
+    W = _g24_graph(g, 600)
+    ti, lab = lo.training_set(g, 600)
+    for a in lo.ALPHAS:
+        u, it = orc.randomwalk_fit(W, ti, lab, alpha=a, return_iters=True)
+        assert it == int(g['rw_alpha%s_iters' % a]) and np.array_equal(u, g['rw_alpha%s_u' % a]), a
