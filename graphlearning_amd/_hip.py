@@ -243,9 +243,14 @@ def check(rc, what=''):
         raise GlxError('%s failed (%d): %s' % (what or 'libglx call', rc, msg.decode() if msg else '?'))
 
 
+def call(name, *args):
+    """The library function `name` on `args`; a non-zero status raises GlxError with that name and the library's message."""
+    check(getattr(load(), name)(*args), name)
+
+
 def device_count():
     n = C.c_int(0)
-    check(load().glx_device_count(C.byref(n)), 'glx_device_count')
+    call('glx_device_count', C.byref(n))
     return n.value
 
 
@@ -325,7 +330,7 @@ class _PinnedPool:
         if ptr is None:
             p = _vp()
             try:
-                check(load().glx_host_alloc(nbytes, C.byref(p)), 'glx_host_alloc')
+                call('glx_host_alloc', nbytes, C.byref(p))
             except BaseException:
                 with self.lock:
                     self.total -= nbytes
@@ -354,35 +359,35 @@ PINNED_RESULTS = True
 
 
 def pool_set_enabled(enabled):
-    check(load().glx_pool_set_enabled(1 if enabled else 0), 'glx_pool_set_enabled')
+    call('glx_pool_set_enabled', 1 if enabled else 0)
 
 
 def debug_set(flags):
-    check(load().glx_debug_set(int(flags)), 'glx_debug_set')
+    call('glx_debug_set', int(flags))
 
 
 def debug_counters():
     out = (C.c_uint64 * 4)()
-    check(load().glx_debug_counters(out), 'glx_debug_counters')
+    call('glx_debug_counters', out)
     return dict(uploads_checked=int(out[0]), engine_readback_differs=int(out[1]), kernel_readback_differs=int(out[2]), bytes_differing=int(out[3]))
 
 
 def upload_set_mode(mode):
     """0 staged + checked (default), 1 staged, 2 straight from the caller's pageable memory (rounds 1-5)."""
-    check(load().glx_upload_set_mode(int(mode)), 'glx_upload_set_mode')
+    call('glx_upload_set_mode', int(mode))
 
 
 def upload_stats():
     """The checked uploads of this process: how many were checked, how many arrived with a wrong sum, how many of those were repaired by a
     repeat, how many given up (glx_upload_stats)."""
     out = (C.c_uint64 * 4)()
-    check(load().glx_upload_stats(out), 'glx_upload_stats')
+    call('glx_upload_stats', out)
     return dict(checked=int(out[0]), wrong_sums=int(out[1]), repaired=int(out[2]), given_up=int(out[3]))
 
 
 def pool_set_poison(byte):
     """Debugging aid: work buffers are filled with `byte` (0 .. 255) when handed out; None / -1 switches it off."""
-    check(load().glx_pool_set_poison(-1 if byte is None else int(byte)), 'glx_pool_set_poison')
+    call('glx_pool_set_poison', -1 if byte is None else int(byte))
 
 
 def pinned_empty(shape, dtype):
@@ -426,9 +431,71 @@ def pinned_reserve(specs):
     return _Join()
 
 
-class DeviceGraph:
+# Communicators and distributed sweeps that are still open when the interpreter shuts down are ABANDONED, not destroyed:
+# tearing an RCCL communicator (or the streams and captured graphs that carry its kernels) down from a garbage-collection
+# pass during interpreter finalisation was seen to hang the process (a failed test that never reached close(), round 3);
+# the operating system reclaims everything at exit anyway.  close() during normal operation destroys as before.
+import atexit
+import weakref
+_abandoned_at_exit = weakref.WeakSet()      # the open objects of the classes that set `_abandon_at_exit`
+
+
+def _abandon_dist_objects():
+    for obj in list(_abandoned_at_exit):
+        try:
+            obj._h = _vp()
+        except Exception:
+            pass
+
+
+atexit.register(_abandon_dist_objects)
+
+
+class _Handle:
+    """Owner of one object of the library: the handle `_h`, opened by the create function a subclass names in `_open` and
+    destroyed by the function the subclass names in `_destroy`.  A context manager; close() may be called twice, and every
+    later use is refused with GlxError before the library is entered."""
+
+    _destroy = None                 # name of the library function that takes the handle back
+    _abandon_at_exit = False        # True: an object still open at interpreter exit is left to the operating system (above)
+
+    def _open(self, name, *args):
+        """Create function `name` on `args`; its last parameter, the handle it hands out, is added here."""
+        self._h = _vp()
+        call(name, *args, C.byref(self._h))
+        if self._abandon_at_exit:
+            _abandoned_at_exit.add(self)
+
+    def _handle(self):
+        if not self._h.value:
+            raise GlxError('%s: the object is closed' % type(self).__name__)
+        return self._h
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            lib = load(required=False)
+            if lib is not None:
+                getattr(lib, self._destroy)(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceGraph(_Handle):
     """A sparse operator resident in HBM (glx_graph).  `A` is any scipy sparse matrix;
     the CSR entry order is preserved (see include/glx.h)."""
+
+    _destroy = 'glx_graph_destroy'
 
     def __init__(self, A, dtype=np.float64, device=None, shape=None, keep_order=False, order=None):
         from scipy import sparse
@@ -440,21 +507,17 @@ class DeviceGraph:
         rowptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
         col = np.ascontiguousarray(A.indices, dtype=np.int32)
         val = np.ascontiguousarray(A.data, dtype=np.float64)
-        self._h = _vp()
-        lib = load()
-        check(lib.glx_graph_create(self.shape[0], self.shape[1], self.nnz, _ptr(rowptr), _ptr(col), _ptr(val),
-                                   _dt(self.dtype), device, C.byref(self._h)), 'glx_graph_create')
+        self._open('glx_graph_create', self.shape[0], self.shape[1], self.nnz, _ptr(rowptr), _ptr(col), _ptr(val), _dt(self.dtype), device)
         self._set_order(order, keep_order)
 
     def _set_order(self, order, keep_order):
-        lib = load()
         if order is not None:       # the caller's locality order (perm[new] = old) instead of the library's pass over the graph
             perm = np.ascontiguousarray(order, dtype=np.int32)
             if perm.shape != (self.shape[0],):
                 raise GlxError('order must be a permutation of the %d rows' % self.shape[0])
-            check(lib.glx_graph_set_order(self._h, _ptr(perm)), 'glx_graph_set_order')
+            call('glx_graph_set_order', self._handle(), _ptr(perm))
         elif keep_order:
-            check(lib.glx_graph_set_order(self._h, None), 'glx_graph_set_order')
+            call('glx_graph_set_order', self._handle(), None)
 
     @classmethod
     def resident(cls, A, dtype=np.float64, device=None, keep_order=False, order=None, want_row_sums=False):
@@ -470,26 +533,25 @@ class DeviceGraph:
         col = np.ascontiguousarray(A.indices, dtype=np.int32)
         val = np.ascontiguousarray(A.data, dtype=np.float64)
         sums = np.empty(self.shape[0], dtype=np.float64) if want_row_sums else None
-        self._h = _vp()
-        check(load().glx_graph_create_resident(self.shape[0], self.shape[1], self.nnz, _ptr(rowptr), _ptr(col), _ptr(val),
-                                               _dt(self.dtype), device, _ptr(sums), C.byref(self._h)), 'glx_graph_create_resident')
+        self._open('glx_graph_create_resident', self.shape[0], self.shape[1], self.nnz, _ptr(rowptr), _ptr(col), _ptr(val), _dt(self.dtype), device,
+                   _ptr(sums))
         self._set_order(order, keep_order)
         return self, sums
 
     def set_row_transform(self, row_scale=None, reverse_rows=False):
         sc = None if row_scale is None else _dense(row_scale, np.float64, (self.shape[0],), 'row_scale')
-        check(load().glx_graph_set_row_transform(self._h, _ptr(sc), 1 if reverse_rows else 0), 'glx_graph_set_row_transform')
+        call('glx_graph_set_row_transform', self._handle(), _ptr(sc), 1 if reverse_rows else 0)
 
     def info(self):
         out = (C.c_int64 * 8)()
-        check(load().glx_graph_info(self._h, out), 'glx_graph_info')
+        call('glx_graph_info', self._handle(), out)
         keys = ['n_rows', 'n_cols', 'nnz', 'stored', 'slices', 'rows_per_slice', 'max_row', 'renumbered']
         return dict(zip(keys, list(out)[:8]))
 
     def order(self):
         """perm[new] = caller's row: the vertex order the library keeps its records in."""
         perm = np.empty(self.shape[0], dtype=np.int32)
-        check(load().glx_graph_order(self._h, _ptr(perm)), 'glx_graph_order')
+        call('glx_graph_order', self._handle(), _ptr(perm))
         return perm
 
     def spmm_bias(self, u, Db=None, iters=1):
@@ -502,7 +564,7 @@ class DeviceGraph:
         Cc = u.shape[1]
         Dbc = None if Db is None else _dense(Db, self.dtype, (self.shape[0], Cc), 'Db')
         out = np.empty((self.shape[0], Cc), dtype=self.dtype)
-        check(load().glx_spmm_bias(self._h, _ptr(Dbc), _ptr(u), _ptr(out), Cc, iters), 'glx_spmm_bias')
+        call('glx_spmm_bias', self._handle(), _ptr(Dbc), _ptr(u), _ptr(out), Cc, iters)
         return out
 
     def poisson_sweep(self, Db, w0, deg, vinf, min_iter=50, max_iter=1000):
@@ -513,8 +575,7 @@ class DeviceGraph:
         vinf = _dense(vinf, np.float64, (n,), 'vinf')
         out = np.empty((n, Cc), dtype=self.dtype)
         T = C.c_int(0)
-        check(load().glx_poisson_sweep(self._h, _ptr(Db), _ptr(w0), _ptr(deg), _ptr(vinf), Cc, min_iter, max_iter,
-                                       _ptr(out), C.byref(T)), 'glx_poisson_sweep')
+        call('glx_poisson_sweep', self._handle(), _ptr(Db), _ptr(w0), _ptr(deg), _ptr(vinf), Cc, min_iter, max_iter, _ptr(out), C.byref(T))
         return out, T.value
 
     def cg(self, B, tol=1e-10, max_iter=100000, x0=None, reduce='exact'):
@@ -533,8 +594,7 @@ class DeviceGraph:
             flags |= GLX_CG_X0
         it = C.c_int(0)
         err = C.c_double(0)
-        check(load().glx_cg_solve(self._h, _ptr(B), _ptr(X), B.shape[1], float(tol), int(max_iter), flags,
-                                  C.byref(it), C.byref(err)), 'glx_cg_solve')
+        call('glx_cg_solve', self._handle(), _ptr(B), _ptr(X), B.shape[1], float(tol), int(max_iter), flags, C.byref(it), C.byref(err))
         return (X[:, 0] if squeeze else X), it.value, err.value
 
     def affine_iterate(self, u0, b=None, tol=1e-10, max_iter=1000000):
@@ -549,8 +609,8 @@ class DeviceGraph:
         out = np.empty_like(u0)
         it = C.c_int64(0)
         err = C.c_double(0)
-        check(load().glx_affine_iterate(self._h, _ptr(b) if b is not None else None, _ptr(u0), _ptr(out), u0.shape[1], float(tol),
-                                        int(max_iter), C.byref(it), C.byref(err)), 'glx_affine_iterate')
+        call('glx_affine_iterate', self._handle(), _ptr(b) if b is not None else None, _ptr(u0), _ptr(out), u0.shape[1], float(tol), int(max_iter),
+             C.byref(it), C.byref(err))
         return (out[:, 0] if squeeze else out), it.value, err.value
 
     def cg_groups(self, B, group_cols, tol=1e-10, max_iter=100000, masks=None, reduce='exact'):
@@ -567,8 +627,8 @@ class DeviceGraph:
         its = np.zeros(ng, dtype=np.int32)
         errs = np.zeros(ng, dtype=np.float64)
         if masks is None:
-            check(load().glx_cg_groups_masked(self._h, _ptr(B), _ptr(X), B.shape[1], int(group_cols), None, None, float(tol), int(max_iter),
-                                              flags, its.ctypes.data_as(C.POINTER(C.c_int)), errs.ctypes.data_as(_f64p)), 'glx_cg_groups_masked')
+            call('glx_cg_groups_masked', self._handle(), _ptr(B), _ptr(X), B.shape[1], int(group_cols), None, None, float(tol), int(max_iter), flags,
+                 its.ctypes.data_as(C.POINTER(C.c_int)), errs.ctypes.data_as(_f64p))
             return X, its, errs
         if len(masks) != ng:
             raise GlxError('cg_groups: %d masks for %d systems' % (len(masks), ng))
@@ -578,9 +638,8 @@ class DeviceGraph:
         allrows = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, np.int32), dtype=np.int32)
         for g, r in enumerate(rows):
             B[r, g * group_cols:(g + 1) * group_cols] = 0
-        check(load().glx_cg_groups_masked(self._h, _ptr(B), _ptr(X), B.shape[1], int(group_cols), _ptr(allrows), _ptr(ptr),
-                                          float(tol), int(max_iter), flags, its.ctypes.data_as(C.POINTER(C.c_int)),
-                                          errs.ctypes.data_as(_f64p)), 'glx_cg_groups_masked')
+        call('glx_cg_groups_masked', self._handle(), _ptr(B), _ptr(X), B.shape[1], int(group_cols), _ptr(allrows), _ptr(ptr), float(tol),
+             int(max_iter), flags, its.ctypes.data_as(C.POINTER(C.c_int)), errs.ctypes.data_as(_f64p))
         return X, its, errs
 
     def cg_groups_rows(self, rows, vals, group_cols, masks, out_scale=None, tol=1e-10, max_iter=100000, reduce='exact'):
@@ -601,9 +660,8 @@ class DeviceGraph:
         X = pinned_empty((self.shape[0], Cc), self.dtype)
         its = np.zeros(ng, dtype=np.int32)
         errs = np.zeros(ng, dtype=np.float64)
-        check(load().glx_cg_groups_rows(self._h, len(rows), _ptr(rows), _ptr(vals), _ptr(scale), _ptr(X), Cc, int(group_cols),
-                                        _ptr(allrows), _ptr(ptr), float(tol), int(max_iter), _reduce_flag(reduce),
-                                        its.ctypes.data_as(C.POINTER(C.c_int)), errs.ctypes.data_as(_f64p)), 'glx_cg_groups_rows')
+        call('glx_cg_groups_rows', self._handle(), len(rows), _ptr(rows), _ptr(vals), _ptr(scale), _ptr(X), Cc, int(group_cols), _ptr(allrows),
+             _ptr(ptr), float(tol), int(max_iter), _reduce_flag(reduce), its.ctypes.data_as(C.POINTER(C.c_int)), errs.ctypes.data_as(_f64p))
         return X, its, errs
 
     def last_block_stats(self):
@@ -616,28 +674,15 @@ class DeviceGraph:
 
     def _block_stats(self):
         out = (C.c_int * 4)()
-        check(load().glx_cg_last_block_stats(self._h, out), 'glx_cg_last_block_stats')
+        call('glx_cg_last_block_stats', self._handle(), out)
         return tuple(out)
 
     def last_stop_margin(self):
         """How close the stop decisions of the last tolerance-mode solve on this operator came to going the other way (relative to
         tol; inf: no such solve)."""
         m = C.c_double(0)
-        check(load().glx_cg_last_stop_margin(self._h, C.byref(m)), 'glx_cg_last_stop_margin')
+        call('glx_cg_last_stop_margin', self._handle(), C.byref(m))
         return m.value
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_graph_destroy(self._h)
-            self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def host_fingerprint(arrays):
@@ -649,7 +694,7 @@ def host_fingerprint(arrays):
     out = (C.c_uint64 * 2)()
     acc = 0
     for a in arrays:
-        check(lib.glx_host_fingerprint(_ptr(a), a.nbytes, acc & 0xffffffffffffffff, out), 'glx_host_fingerprint')
+        call('glx_host_fingerprint', _ptr(a), a.nbytes, acc & 0xffffffffffffffff, out)
         acc = out[0] ^ ((out[1] * 0x9e3779b97f4a7c15) & 0xffffffffffffffff)
     return (int(out[0]), int(out[1]))
 
@@ -664,28 +709,27 @@ def _reduce_flag(reduce):
     raise GlxError("reduce must be 'exact' (reference-order reductions) or 'tree' (tolerance mode), got %r" % (reduce,))
 
 
-class Sweep:
+class Sweep(_Handle):
     """Prepared Poisson / heat sweep (glx_sweep): device-resident state, repeated runs."""
+
+    _destroy = 'glx_sweep_destroy'
 
     def __init__(self, graph, Cc, min_iter=50, max_iter=1000, use_hipgraph=True):
         self.graph = graph
         self.C = Cc
-        self._h = _vp()
-        check(load().glx_sweep_create(graph._h, Cc, min_iter, max_iter, 1 if use_hipgraph else 0, C.byref(self._h)),
-              'glx_sweep_create')
+        self.generation = 0
+        self._open('glx_sweep_create', graph._handle(), Cc, min_iter, max_iter, 1 if use_hipgraph else 0)
 
     def set_problem(self, Db, w0, deg, vinf):
         n = self.graph.shape[0]
         Db = _dense(Db, self.graph.dtype, (n, self.C), 'Db')
-        check(load().glx_sweep_set_problem(self._h, _ptr(Db), _ptr(_dense(w0, np.float64, (n,))),
-                                           _ptr(_dense(deg, np.float64, (n,))), _ptr(_dense(vinf, np.float64, (n,)))),
-              'glx_sweep_set_problem')
+        call('glx_sweep_set_problem', self._handle(), _ptr(Db), _ptr(_dense(w0, np.float64, (n,))), _ptr(_dense(deg, np.float64, (n,))),
+             _ptr(_dense(vinf, np.float64, (n,))))
 
     def set_vectors(self, deg, vinf):
         """The graph's own vectors of the stop test (ssl.py:642-643), uploaded once per prepared sweep."""
         n = self.graph.shape[0]
-        check(load().glx_sweep_set_vectors(self._h, _ptr(_dense(deg, np.float64, (n,))), _ptr(_dense(vinf, np.float64, (n,)))),
-              'glx_sweep_set_vectors')
+        call('glx_sweep_set_vectors', self._handle(), _ptr(_dense(deg, np.float64, (n,))), _ptr(_dense(vinf, np.float64, (n,))))
 
     def set_problem_rows(self, rows, Db_rows, w0_rows, err0):
         """A new training set: the labelled rows, their rows of Db = D^-1 b and of w0 = v0/deg, and
@@ -694,30 +738,29 @@ class Sweep:
         m = len(rows)
         Db_rows = _dense(Db_rows, self.graph.dtype, (m, self.C), 'Db_rows')
         w0_rows = _dense(w0_rows, np.float64, (m,), 'w0_rows')
-        check(load().glx_sweep_set_problem_rows(self._h, m, _ptr(rows), _ptr(Db_rows), _ptr(w0_rows), float(err0)),
-              'glx_sweep_set_problem_rows')
+        call('glx_sweep_set_problem_rows', self._handle(), m, _ptr(rows), _ptr(Db_rows), _ptr(w0_rows), float(err0))
 
     def run(self):
         T = C.c_int(0)
         ms = C.c_float(0)
-        check(load().glx_sweep_run(self._h, C.byref(T), C.byref(ms)), 'glx_sweep_run')
-        self.generation = getattr(self, 'generation', 0) + 1
+        call('glx_sweep_run', self._handle(), C.byref(T), C.byref(ms))
+        self.generation += 1
         return T.value, ms.value
 
     def stop_values(self):
         """(first, values): the stop values max|v_t - v_inf| the last run() compared with 1/n, t = first, first+1, ..."""
         first, count = C.c_int(0), C.c_int(0)
-        check(load().glx_sweep_stop_values(self._h, 0, None, C.byref(first), C.byref(count)), 'glx_sweep_stop_values')
+        call('glx_sweep_stop_values', self._handle(), 0, None, C.byref(first), C.byref(count))
         vals = np.empty(count.value, dtype=np.float64)
-        check(load().glx_sweep_stop_values(self._h, len(vals), _ptr(vals), C.byref(first), C.byref(count)), 'glx_sweep_stop_values')
+        call('glx_sweep_stop_values', self._handle(), len(vals), _ptr(vals), C.byref(first), C.byref(count))
         return first.value, vals
 
     def set_state(self, u0, Db=None):
         n = self.graph.shape[0]
         u0 = None if u0 is None else _dense(u0, self.graph.dtype, (n, self.C), 'u0')
         Db = None if Db is None else _dense(Db, self.graph.dtype, (n, self.C), 'Db')
-        check(load().glx_sweep_set_state(self._h, _ptr(u0), _ptr(Db)), 'glx_sweep_set_state')
-        self.generation = getattr(self, 'generation', 0) + 1
+        call('glx_sweep_set_state', self._handle(), _ptr(u0), _ptr(Db))
+        self.generation += 1
 
     def set_state_labels(self, labels, rows, Db_rows):
         """u = onehot(labels), bias = its m nonzero rows (distinct `rows`): n labels and m rows go up instead of two dense arrays."""
@@ -725,16 +768,16 @@ class Sweep:
         labels = _dense(labels, np.int64, (n,), 'labels')
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
         Db_rows = _dense(Db_rows, self.graph.dtype, (len(rows), self.C), 'Db_rows')
-        check(load().glx_sweep_set_state_labels(self._h, _ptr(labels), len(rows), _ptr(rows), _ptr(Db_rows)), 'glx_sweep_set_state_labels')
-        self.generation = getattr(self, 'generation', 0) + 1
+        call('glx_sweep_set_state_labels', self._handle(), _ptr(labels), len(rows), _ptr(rows), _ptr(Db_rows))
+        self.generation += 1
 
     def iterate(self, iters):
-        check(load().glx_sweep_iterate(self._h, int(iters)), 'glx_sweep_iterate')
-        self.generation = getattr(self, 'generation', 0) + 1
+        call('glx_sweep_iterate', self._handle(), int(iters))
+        self.generation += 1
 
     def fetch(self):
         out = pinned_empty((self.graph.shape[0], self.C), self.graph.dtype)
-        check(load().glx_sweep_fetch(self._h, _ptr(out)), 'glx_sweep_fetch')
+        call('glx_sweep_fetch', self._handle(), _ptr(out))
         return out
 
     def project(self, priors=None, weights=None, max_steps=0, similarity=True, to_onehot=False, want_labels=True, then_iterate=0):
@@ -747,77 +790,61 @@ class Sweep:
         labels = pinned_empty((n,), np.int64) if want_labels else None
         err = C.c_double(0)
         steps = C.c_int(0)
-        check(load().glx_sweep_project_iterate(self._h, _ptr(pri), _ptr(w), _ptr(labels) if want_labels else None, C.byref(err),
-                                               C.byref(steps), int(max_steps), 1 if similarity else 0, 1 if to_onehot else 0,
-                                               int(then_iterate)), 'glx_sweep_project_iterate')
+        call('glx_sweep_project_iterate', self._handle(), _ptr(pri), _ptr(w), _ptr(labels) if want_labels else None, C.byref(err), C.byref(steps),
+             int(max_steps), 1 if similarity else 0, 1 if to_onehot else 0, int(then_iterate))
         if to_onehot or then_iterate:
-            self.generation = getattr(self, 'generation', 0) + 1
+            self.generation += 1
         return labels, w, err.value, steps.value
 
     def launches(self):
         n = C.c_int64(0)
-        check(load().glx_sweep_launches(self._h, C.byref(n)), 'glx_sweep_launches')
+        call('glx_sweep_launches', self._handle(), C.byref(n))
         return n.value
 
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_sweep_destroy(self._h)
-            self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SweepGroups:
+class SweepGroups(_Handle):
     """Several training sets as column groups of ONE prepared Poisson sweep (glx_sweep_groups): trial b owns columns
     b C .. b C + C - 1, its own stop value and its own stop test; every trial's iterate and T are those of its own fit."""
+
+    _destroy = 'glx_sweep_groups_destroy'
 
     def __init__(self, graph, Cc, B, min_iter=50, max_iter=1000):
         self.graph = graph
         self.C = Cc
         self.B = B
         self.generation = 0
-        self._h = _vp()
-        check(load().glx_sweep_groups_create(graph._h, Cc, B, min_iter, max_iter, C.byref(self._h)), 'glx_sweep_groups_create')
+        self._open('glx_sweep_groups_create', graph._handle(), Cc, B, min_iter, max_iter)
 
     def set_vectors(self, deg, vinf):
         n = self.graph.shape[0]
-        check(load().glx_sweep_groups_set_vectors(self._h, _ptr(_dense(deg, np.float64, (n,))), _ptr(_dense(vinf, np.float64, (n,)))),
-              'glx_sweep_groups_set_vectors')
+        call('glx_sweep_groups_set_vectors', self._handle(), _ptr(_dense(deg, np.float64, (n,))), _ptr(_dense(vinf, np.float64, (n,))))
 
     def set_problem_rows(self, b, rows, Db_rows, w0_rows, err0):
         rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
         m = len(rows)
         Db_rows = _dense(Db_rows, self.graph.dtype, (m, self.C), 'Db_rows')
         w0_rows = _dense(w0_rows, np.float64, (m,), 'w0_rows')
-        check(load().glx_sweep_groups_set_problem_rows(self._h, int(b), m, _ptr(rows), _ptr(Db_rows), _ptr(w0_rows), float(err0)),
-              'glx_sweep_groups_set_problem_rows')
+        call('glx_sweep_groups_set_problem_rows', self._handle(), int(b), m, _ptr(rows), _ptr(Db_rows), _ptr(w0_rows), float(err0))
 
     def run(self, used=None):
         """Returns (T per group in use, device ms)."""
         used = self.B if used is None else int(used)
         T = (C.c_int * self.B)()
         ms = C.c_float(0)
-        check(load().glx_sweep_groups_run(self._h, used, T, C.byref(ms)), 'glx_sweep_groups_run')
+        call('glx_sweep_groups_run', self._handle(), used, T, C.byref(ms))
         self.generation += 1
         return [int(T[b]) for b in range(used)], ms.value
 
     def stop_values(self, b):
         first, count = C.c_int(0), C.c_int(0)
-        check(load().glx_sweep_groups_stop_values(self._h, int(b), 0, None, C.byref(first), C.byref(count)), 'glx_sweep_groups_stop_values')
+        call('glx_sweep_groups_stop_values', self._handle(), int(b), 0, None, C.byref(first), C.byref(count))
         vals = np.empty(count.value, dtype=np.float64)
-        check(load().glx_sweep_groups_stop_values(self._h, int(b), len(vals), _ptr(vals), C.byref(first), C.byref(count)),
-              'glx_sweep_groups_stop_values')
+        call('glx_sweep_groups_stop_values', self._handle(), int(b), len(vals), _ptr(vals), C.byref(first), C.byref(count))
         return first.value, vals
 
     def fetch(self, b):
         out = pinned_empty((self.graph.shape[0], self.C), self.graph.dtype)
-        check(load().glx_sweep_groups_fetch(self._h, int(b), _ptr(out)), 'glx_sweep_groups_fetch')
+        call('glx_sweep_groups_fetch', self._handle(), int(b), _ptr(out))
         return out
 
     def project(self, b, priors=None, weights=None, max_steps=0, similarity=True, want_labels=True):
@@ -827,30 +854,17 @@ class SweepGroups:
         labels = pinned_empty((n,), np.int64) if want_labels else None
         err = C.c_double(0)
         steps = C.c_int(0)
-        check(load().glx_sweep_groups_project(self._h, int(b), _ptr(pri), _ptr(w), _ptr(labels) if want_labels else None, C.byref(err),
-                                              C.byref(steps), int(max_steps), 1 if similarity else 0), 'glx_sweep_groups_project')
+        call('glx_sweep_groups_project', self._handle(), int(b), _ptr(pri), _ptr(w), _ptr(labels) if want_labels else None, C.byref(err),
+             C.byref(steps), int(max_steps), 1 if similarity else 0)
         return labels, w, err.value, steps.value
 
     def launches(self):
         n = C.c_int64(0)
-        check(load().glx_sweep_groups_launches(self._h, C.byref(n)), 'glx_sweep_groups_launches')
+        call('glx_sweep_groups_launches', self._handle(), C.byref(n))
         return n.value
 
     def view(self, b):
         return GroupView(self, b)
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_sweep_groups_destroy(self._h)
-            self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class GroupView:
@@ -877,63 +891,31 @@ class GroupView:
         return self.groups.project(self.b, priors, weights, max_steps=max_steps, similarity=similarity, want_labels=want_labels)
 
 
-# Communicators and distributed sweeps that are still open when the interpreter shuts down are ABANDONED, not destroyed:
-# tearing an RCCL communicator (or the streams and captured graphs that carry its kernels) down from a garbage-collection
-# pass during interpreter finalisation was seen to hang the process (a failed test that never reached close(), round 3);
-# the operating system reclaims everything at exit anyway.  close() during normal operation destroys as before.
-import atexit
-import weakref
-_live_dist_objects = weakref.WeakSet()
-
-
-def _abandon_dist_objects():
-    for obj in list(_live_dist_objects):
-        try:
-            obj._h = _vp()
-        except Exception:
-            pass
-
-
-atexit.register(_abandon_dist_objects)
-
-
-class Comm:
+class Comm(_Handle):
     """One rank's libglx-owned RCCL communicator (glx_comm).  `uid`: the 128 bytes of Comm.unique_id() made on rank 0
     and shipped to every rank; uid=None with nranks == 1 gives a transport-free single rank."""
+
+    _destroy = 'glx_dist_destroy'
+    _abandon_at_exit = True
 
     @staticmethod
     def unique_id():
         buf = C.create_string_buffer(128)
-        check(load().glx_dist_unique_id(buf), 'glx_dist_unique_id')
+        call('glx_dist_unique_id', buf)
         return buf.raw
 
     def __init__(self, nranks=1, rank=0, uid=None, device=None):
         self.nranks, self.rank, self.device = int(nranks), int(rank), _dev(device)
-        self._h = _vp()
         idbuf = None if uid is None else C.create_string_buffer(bytes(uid), 128)
-        check(load().glx_dist_init_rank(self.nranks, self.rank, idbuf, self.device, C.byref(self._h)), 'glx_dist_init_rank')
-        _live_dist_objects.add(self)
+        self._open('glx_dist_init_rank', self.nranks, self.rank, idbuf, self.device)
 
     def info(self):
         info = (C.c_int32 * 4)()
-        check(load().glx_dist_comm_info(self._h, info), 'glx_dist_comm_info')
+        call('glx_dist_comm_info', self._handle(), info)
         return dict(rank=int(info[0]), nranks=int(info[1]), device=int(info[2]), rccl=bool(info[3]))
 
     def has_transport(self):
         return self.info()['rccl']
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_dist_destroy(self._h)
-            self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # glx_dist_sweep_create's form flags (include/glx.h): what the library picks by itself, and the forms tests force
@@ -941,9 +923,12 @@ DIST_FORMS = {'auto': 0, 'split': 2, 'split_pack': 2 | 8, 'split_inline': 2 | 16
 DIST_GATHER = 256        # GLX_DIST_FORM_GATHER: the exchange is one in-place all-gather of the ranks' blocks (dist.GatherPlan)
 
 
-class DistSweep:
+class DistSweep(_Handle):
     """One rank's share of the vertex-partitioned Poisson sweep (glx_dist_sweep): local operator (boundary rows first,
     columns [owned | halo]), exchange lists, device state; every sweep and every collective is enqueued by libglx."""
+
+    _destroy = 'glx_dist_sweep_destroy'
+    _abandon_at_exit = True
 
     def __init__(self, comm, P_local, n_boundary, send_counts, send_idx, recv_counts, n_global, Cc, dtype=np.float64,
                  force_exchange=False, use_hipgraph=True, form='auto', gather_cap=None):
@@ -965,42 +950,36 @@ class DistSweep:
         rcnt = np.ascontiguousarray(recv_counts, dtype=np.int64)
         si = np.ascontiguousarray(send_idx, dtype=np.int32)
         self.n_send = int(sc.sum()) if gather_cap is None else self.gather_cap
-        self._h = _vp()
         flags = (1 if use_hipgraph else 0) | DIST_FORMS[form] | (DIST_GATHER if gather_cap is not None else 0)
-        check(load().glx_dist_sweep_create(comm._h, self.n_own, self.n_halo, int(n_boundary), _ptr(rowptr), _ptr(col), _ptr(val),
-                                           _dt(self.dtype), self.C, _ptr(sc), _ptr(si), _ptr(rcnt), int(n_global),
-                                           1 if force_exchange else 0, flags, C.byref(self._h)),
-              'glx_dist_sweep_create')
-        _live_dist_objects.add(self)
+        self._open('glx_dist_sweep_create', comm._handle(), self.n_own, self.n_halo, int(n_boundary), _ptr(rowptr), _ptr(col), _ptr(val),
+                   _dt(self.dtype), self.C, _ptr(sc), _ptr(si), _ptr(rcnt), int(n_global), 1 if force_exchange else 0, flags)
 
     def set_problem(self, Db_own, w0_own, deg_own, vinf_own):
         n = self.n_own
         Db = None if Db_own is None else _dense(Db_own, self.dtype, (n, self.C), 'Db_own')
-        check(load().glx_dist_sweep_set_problem(self._h, _ptr(Db), _ptr(_dense(w0_own, np.float64, (n,))),
-                                                _ptr(_dense(deg_own, np.float64, (n,))), _ptr(_dense(vinf_own, np.float64, (n,)))),
-              'glx_dist_sweep_set_problem')
+        call('glx_dist_sweep_set_problem', self._handle(), _ptr(Db), _ptr(_dense(w0_own, np.float64, (n,))), _ptr(_dense(deg_own, np.float64, (n,))),
+             _ptr(_dense(vinf_own, np.float64, (n,))))
 
     def run(self, min_iter=50, max_iter=1000, check_every=8, err0=0.0):
         T = C.c_int(0)
         ms = C.c_float(0)
-        check(load().glx_poisson_sweep_dist(self._h, int(min_iter), int(max_iter), int(check_every), float(err0), C.byref(T),
-                                            C.byref(ms)), 'glx_poisson_sweep_dist')
+        call('glx_poisson_sweep_dist', self._handle(), int(min_iter), int(max_iter), int(check_every), float(err0), C.byref(T), C.byref(ms))
         return T.value, ms.value
 
     def fetch(self):
         out = np.empty((self.n_own, self.C), dtype=self.dtype)
-        check(load().glx_dist_sweep_fetch(self._h, _ptr(out)), 'glx_dist_sweep_fetch')
+        call('glx_dist_sweep_fetch', self._handle(), _ptr(out))
         return out
 
     def stats(self):
         out = (C.c_int64 * 4)()
-        check(load().glx_dist_sweep_stats(self._h, out), 'glx_dist_sweep_stats')
+        call('glx_dist_sweep_stats', self._handle(), out)
         return dict(sweeps=out[0], exchanges=out[1], graphs=out[2], exchanging=bool(out[3]))
 
     def info(self):
         """What the object decided (glx_dist_sweep_info): captured / eager exchanging sweeps, the self-test's verdict, ..."""
         out = (C.c_int64 * 8)()
-        check(load().glx_dist_sweep_info(self._h, out), 'glx_dist_sweep_info')
+        call('glx_dist_sweep_info', self._handle(), out)
         cap = {1: 'captured', 0: 'eager', -1: 'undecided'}[int(out[1])]
         return dict(exchanging=bool(out[0]), exchange=cap if out[0] else 'none', selftest={0: 'not run', 1: 'passed', 2: 'failed'}[int(out[2])],
                     overlap=bool(out[3]), fused=bool(out[4]), scatter=bool(out[5]), send_records=int(out[6]), halo_records=int(out[7]))
@@ -1008,42 +987,29 @@ class DistSweep:
     def time_parts(self, reps=50):
         """Microseconds of the rank-local pieces of one sweep, each timed alone (glx_dist_sweep_time_parts)."""
         out = (C.c_float * 4)()
-        check(load().glx_dist_sweep_time_parts(self._h, int(reps), out), 'glx_dist_sweep_time_parts')
+        call('glx_dist_sweep_time_parts', self._handle(), int(reps), out)
         return dict(boundary_us=float(out[0]), interior_us=float(out[1]), pack_us=float(out[2]), both_us=float(out[3]))
 
     # stepwise form (transport left to the caller)
     def begin(self):
-        check(load().glx_dist_sweep_begin(self._h), 'glx_dist_sweep_begin')
+        call('glx_dist_sweep_begin', self._handle())
 
     def boundary(self, want_err):
-        check(load().glx_dist_sweep_boundary(self._h, 1 if want_err else 0), 'glx_dist_sweep_boundary')
+        call('glx_dist_sweep_boundary', self._handle(), 1 if want_err else 0)
 
     def get_send(self):
         out = np.empty((self.n_send, self.lay['ld']), dtype=self.dtype)
-        check(load().glx_dist_sweep_get_send(self._h, _ptr(out)), 'glx_dist_sweep_get_send')
+        call('glx_dist_sweep_get_send', self._handle(), _ptr(out))
         return out
 
     def put_halo(self, rec, next_iterate):
         rec = _dense(rec, self.dtype, (self.n_halo, self.lay['ld']), 'halo records')
-        check(load().glx_dist_sweep_put_halo(self._h, _ptr(rec), 1 if next_iterate else 0), 'glx_dist_sweep_put_halo')
+        call('glx_dist_sweep_put_halo', self._handle(), _ptr(rec), 1 if next_iterate else 0)
 
     def interior(self, want_err):
         e = C.c_double(0)
-        check(load().glx_dist_sweep_interior(self._h, 1 if want_err else 0, C.byref(e)), 'glx_dist_sweep_interior')
+        call('glx_dist_sweep_interior', self._handle(), 1 if want_err else 0, C.byref(e))
         return e.value if want_err else None
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_dist_sweep_destroy(self._h)
-            self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def nearest_dist(X, idx, device=None):
@@ -1055,14 +1021,14 @@ def nearest_dist(X, idx, device=None):
         raise GlxError('nearest_dist: X must be (n, d)')
     idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
     out = np.empty(X.shape[0], dtype=np.float64)
-    check(load().glx_nearest_dist(_ptr(X), X.shape[0], X.shape[1], _ptr(idx), len(idx), _ptr(out), _dev(device)), 'glx_nearest_dist')
+    call('glx_nearest_dist', _ptr(X), X.shape[0], X.shape[1], _ptr(idx), len(idx), _ptr(out), _dev(device))
     return out
 
 
 def record_layout(Cc, dtype=np.float64, has_w=True):
     """Vertex-record layout of the dense operands (pure host call, no GPU needed)."""
     out = (C.c_int32 * 6)()
-    check(load().glx_record_layout(int(Cc), _dt(dtype), 1 if has_w else 0, out), 'glx_record_layout')
+    call('glx_record_layout', int(Cc), _dt(dtype), 1 if has_w else 0, out)
     return dict(ld=out[0], woff=out[1], rec_bytes=out[2], G=out[3], nvec=out[4], esize=out[5])
 
 
@@ -1078,8 +1044,8 @@ def argmax_project(prob, priors=None, weights=None, max_steps=0, similarity=True
     labels = np.empty(n, dtype=np.int64)
     err = C.c_double(0)
     steps = C.c_int(0)
-    check(load().glx_argmax_project_t(_ptr(prob), _dt(prob.dtype), n, Cc, _ptr(pri), _ptr(w), _ptr(labels), C.byref(err),
-                                      C.byref(steps), int(max_steps), 1 if similarity else 0, _dev(device)), 'glx_argmax_project')
+    call('glx_argmax_project_t', _ptr(prob), _dt(prob.dtype), n, Cc, _ptr(pri), _ptr(w), _ptr(labels), C.byref(err), C.byref(steps), int(max_steps),
+         1 if similarity else 0, _dev(device))
     return labels, w, err.value, steps.value
 
 
@@ -1089,8 +1055,8 @@ def lp_iterate(uu, ul, nbr, row, W, ind, val, p, T, tol, device=None):
         if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags['C_CONTIGUOUS']):
             raise GlxError('lp_iterate: arrays must be C-contiguous with the dtypes of the reference binding')
     it = C.c_int64(0)
-    check(load().glx_lp_iterate(_ptr(uu), _ptr(ul), _ptr(nbr), _ptr(row), _ptr(W), _ptr(ind), _ptr(val), float(p), int(T), float(tol),
-                                len(uu), len(W), len(ind), C.byref(it), _dev(device)), 'glx_lp_iterate')
+    call('glx_lp_iterate', _ptr(uu), _ptr(ul), _ptr(nbr), _ptr(row), _ptr(W), _ptr(ind), _ptr(val), float(p), int(T), float(tol), len(uu), len(W),
+         len(ind), C.byref(it), _dev(device))
     return it.value
 
 
@@ -1111,8 +1077,8 @@ def lp_iterate_batch(n, nbr, row, W, ind, val, p, T, tol, device=None):
     uu = np.empty((n, B), dtype=np.float64)
     ul = np.empty((n, B), dtype=np.float64)
     iters = np.zeros(B, dtype=np.int64)
-    check(load().glx_lp_iterate_batch(n, len(nbr), _ptr(nbr), _ptr(row), _ptr(W), B, len(ind), _ptr(ind), _ptr(val), float(p), T, float(tol),
-                                      _ptr(uu), _ptr(ul), _ptr(iters), _dev(device)), 'glx_lp_iterate_batch')
+    call('glx_lp_iterate_batch', n, len(nbr), _ptr(nbr), _ptr(row), _ptr(W), B, len(ind), _ptr(ind), _ptr(val), float(p), T, float(tol), _ptr(uu),
+         _ptr(ul), _ptr(iters), _dev(device))
     return uu, ul, iters
 
 
@@ -1149,9 +1115,8 @@ def sssp(in_ptr, in_idx, in_cost, src_ptr, src_idx, src_val, max_dist=np.inf, ho
     cp = np.empty((n, B), dtype=np.int32) if return_cp else None
     rounds = (C.c_int64 * 2)(0, 0)
     ms = (C.c_double * 4)(0, 0, 0, 0)
-    check(load().glx_sssp(n, len(in_idx), _ptr(in_ptr), _ptr(in_idx), _ptr(in_cost), _ptr(out_ptr), _ptr(out_idx), B, _ptr(src_ptr),
-                          _ptr(src_idx), _ptr(src_val), float(max_dist), GLX_SSSP_HOPF_LAX if hopf_lax else GLX_SSSP_PLAIN, _ptr(dist),
-                          _ptr(cp), rounds, ms, _dev(device)), 'glx_sssp')
+    call('glx_sssp', n, len(in_idx), _ptr(in_ptr), _ptr(in_idx), _ptr(in_cost), _ptr(out_ptr), _ptr(out_idx), B, _ptr(src_ptr), _ptr(src_idx),
+         _ptr(src_val), float(max_dist), GLX_SSSP_HOPF_LAX if hopf_lax else GLX_SSSP_PLAIN, _ptr(dist), _ptr(cp), rounds, ms, _dev(device))
     sssp_last_ms = tuple(ms)
     return dist, cp, (int(rounds[0]), int(rounds[1]))
 
@@ -1183,21 +1148,20 @@ def components(indptr, indices, n, device=None):
     labels = np.empty(n, dtype=np.int32)
     ncomp = C.c_int64(0)
     ms = (C.c_double * 4)(0, 0, 0, 0)
-    check(load().glx_components(n, len(indices), _ptr(indptr), _ptr(indices), _ptr(labels), C.byref(ncomp), ms, _dev(device)),
-          'glx_components')
+    call('glx_components', n, len(indices), _ptr(indptr), _ptr(indices), _ptr(labels), C.byref(ncomp), ms, _dev(device))
     components_last_ms = tuple(ms)
     return int(ncomp.value), labels
 
 
 def components_set_wave_row(min_entries=0):
     """plan override of the calling thread for measurements: rows of at least `min_entries` stored entries take a wavefront (0: the library's)"""
-    check(load().glx_components_set_wave_row(int(min_entries)), 'glx_components_set_wave_row')
+    call('glx_components_set_wave_row', int(min_entries))
 
 
 def components_plan():
     """(threshold in effect, the library's own, vertices per scan tile, rows that took a wavefront in this thread's last call)"""
     out = (C.c_int64 * 4)()
-    check(load().glx_components_plan(out), 'glx_components_plan')
+    call('glx_components_plan', out)
     return tuple(int(v) for v in out)
 
 
@@ -1221,10 +1185,8 @@ def lip_iterate(n, nbr, row, W, ind, val, weighted, alpha, beta, T, tol, device=
     iters = np.zeros(B, dtype=np.int64)
     plan = (C.c_int64 * 3)(0, 0, 0)
     errs = np.full((T, B), np.nan) if want_errors else None
-    check(load().glx_lip_iterate(n, len(nbr), _ptr(nbr), _ptr(row), _ptr(W), B, len(ind), _ptr(ind), _ptr(val), 1 if weighted else 0,
-                                 float(alpha), float(beta), T, float(tol), _ptr(u), _ptr(iters), plan, _ptr(errs), int(small_level),
-                                 _dev(device)),
-          'glx_lip_iterate')
+    call('glx_lip_iterate', n, len(nbr), _ptr(nbr), _ptr(row), _ptr(W), B, len(ind), _ptr(ind), _ptr(val), 1 if weighted else 0, float(alpha),
+         float(beta), T, float(tol), _ptr(u), _ptr(iters), plan, _ptr(errs), int(small_level), _dev(device))
     return u, iters, (int(plan[0]), int(plan[1]), int(plan[2])), errs
 
 
@@ -1256,8 +1218,8 @@ def slp_iterate(row_ptr, col, W, lam, gamma, ind, val, T, device=None, want_hist
     u = np.empty((n, Cc), dtype=np.float64)
     hist = np.empty((T, n, Cc), dtype=np.float64) if want_history else None
     plan = (C.c_int64 * 3)(0, 0, 0)
-    check(load().glx_slp_iterate(n, len(col), _ptr(row_ptr), _ptr(col), _ptr(W), _ptr(lam), _ptr(gamma), Cc, len(ind), _ptr(ind), _ptr(val),
-                                 T, _ptr(u), _ptr(hist) if (want_history and T > 0) else None, plan, _dev(device)), 'glx_slp_iterate')
+    call('glx_slp_iterate', n, len(col), _ptr(row_ptr), _ptr(col), _ptr(W), _ptr(lam), _ptr(gamma), Cc, len(ind), _ptr(ind), _ptr(val), T, _ptr(u),
+         _ptr(hist) if (want_history and T > 0) else None, plan, _dev(device))
     return u, hist, (int(plan[0]), int(plan[1]), int(plan[2]))
 
 
@@ -1289,9 +1251,9 @@ def ck_solve(row_ptr, col, W, ind, val, e, power_it=100, alpha_frac=1.05, tol=1e
                 return 1
         cb = _CK_ITERATE_FN(_each)
     try:
-        check(load().glx_ck_solve(n, len(col), _ptr(row_ptr), _ptr(col), _ptr(W), k, len(ind), _ptr(ind), _ptr(val), _ptr(e), int(power_it),
-                                  float(alpha_frac), float(tol), int(max_it), _ptr(u), C.byref(l), C.byref(T), _ptr(errs) if err_cap else None,
-                                  int(err_cap), C.cast(cb, _vp) if cb is not None else None, None, plan, _dev(device)), 'glx_ck_solve')
+        call('glx_ck_solve', n, len(col), _ptr(row_ptr), _ptr(col), _ptr(W), k, len(ind), _ptr(ind), _ptr(val), _ptr(e), int(power_it),
+             float(alpha_frac), float(tol), int(max_it), _ptr(u), C.byref(l), C.byref(T), _ptr(errs) if err_cap else None, int(err_cap),
+             C.cast(cb, _vp) if cb is not None else None, None, plan, _dev(device))
     except GlxError:
         if raised:
             raise raised[0]
@@ -1315,8 +1277,8 @@ def dlp_solve(row_ptr, col, P, ind, val, alpha=0.05, lam=0.1, T=2, device=None, 
     u = np.empty((n, k), dtype=np.float64)
     hist = np.empty((T, n, k), dtype=np.float64) if (want_history and 1 <= T <= 64) else None
     plan = (C.c_int64 * 4)(0, 0, 0, 0)
-    check(load().glx_dlp_solve(n, len(col), _ptr(row_ptr), _ptr(col), _ptr(P), k, len(ind), _ptr(ind), _ptr(val), float(alpha), float(lam), T,
-                               _ptr(u), _ptr(hist) if hist is not None else None, plan, _dev(device)), 'glx_dlp_solve')
+    call('glx_dlp_solve', n, len(col), _ptr(row_ptr), _ptr(col), _ptr(P), k, len(ind), _ptr(ind), _ptr(val), float(alpha), float(lam), T, _ptr(u),
+         _ptr(hist) if hist is not None else None, plan, _dev(device))
     return u, hist, tuple(int(v) for v in plan)
 
 
@@ -1339,73 +1301,50 @@ def mmbo_solve(X, vals, lab0, ind, lab, k, Ns=6, T=10, dt=0.15, mu=50, device=No
     hist = np.empty((T, n) if ok else (1, 1), dtype=np.int32)
     Z = np.empty((k, m) if ok else (1, 1), dtype=np.float64)
     plan = (C.c_int64 * 7)(0, 0, 0, 0, 0, 0, 0)
-    check(load().glx_mmbo_solve(n, m, _ptr(X), _ptr(vals), _ptr(lab0), len(ind), _ptr(ind), _ptr(lab), k, Ns, T, float(dt), float(mu), _ptr(hist),
-                                _ptr(Z), plan, _dev(device)), 'glx_mmbo_solve')
+    call('glx_mmbo_solve', n, m, _ptr(X), _ptr(vals), _ptr(lab0), len(ind), _ptr(ind), _ptr(lab), k, Ns, T, float(dt), float(mu), _ptr(hist), _ptr(Z),
+         plan, _dev(device))
     return hist, Z, tuple(int(v) for v in plan)
 
 
-class Eig:
+class Eig(_Handle):
     """The device half of the thick-restart Lanczos eigensolver (glx_eig_*, csrc/eig.hip; the contract is DESIGN.md 4.12): a
     symmetric matrix A as canonical CSR arrays (row_ptr, col, val) and a basis of m + 1 column-major Lanczos vectors that stays on
     the device.  The backend interface of graphlearning_amd._eig.thick_restart: set_column, orthonormalize, run, rotate,
     get_columns.  A context manager; close() releases the device memory.  GlxError on every refusal of the library."""
 
+    _destroy = 'glx_eig_destroy'
+
     def __init__(self, row_ptr, col, val, m, device=None):
-        self._h = _vp()
         ok, n, row_ptr, col, val, _, _ = _csr_operands(row_ptr, col, (val,))
         if not (ok and int(row_ptr[-1]) == len(col)):
             raise GlxError('Eig: inconsistent array shapes or sizes')
         self.n, self.m = n, int(m)
-        check(load().glx_eig_create(n, _ptr(row_ptr), _ptr(col), _ptr(val), int(m), _dev(device), C.byref(self._h)), 'glx_eig_create')
-
-    def _handle(self):
-        if not self._h.value:
-            raise GlxError('Eig: the object is closed')
-        return self._h
+        self._open('glx_eig_create', n, _ptr(row_ptr), _ptr(col), _ptr(val), int(m), _dev(device))
 
     def set_column(self, j, x):
         x = _dense(np.asarray(x).ravel(), np.float64, (self.n,), 'column')
-        check(load().glx_eig_set_column(self._handle(), int(j), _ptr(x)), 'glx_eig_set_column')
+        call('glx_eig_set_column', self._handle(), int(j), _ptr(x))
 
     def orthonormalize(self, j):
         norm = C.c_double(0.0)
-        check(load().glx_eig_orthonormalize(self._handle(), int(j), C.byref(norm)), 'glx_eig_orthonormalize')
+        call('glx_eig_orthonormalize', self._handle(), int(j), C.byref(norm))
         return float(norm.value)
 
     def run(self, j0, j1):
         count = max(int(j1) - int(j0), 1)
         alpha, beta = np.empty(count), np.empty(count)
-        check(load().glx_eig_run(self._handle(), int(j0), int(j1), _ptr(alpha), _ptr(beta)), 'glx_eig_run')
+        call('glx_eig_run', self._handle(), int(j0), int(j1), _ptr(alpha), _ptr(beta))
         return alpha, beta
 
     def rotate(self, Y, rows, keep):
         Y = _dense(Y, np.float64, (int(rows), int(keep)), 'Y')
-        check(load().glx_eig_rotate(self._handle(), _ptr(Y), int(rows), int(keep)), 'glx_eig_rotate')
+        call('glx_eig_rotate', self._handle(), _ptr(Y), int(rows), int(keep))
 
     def get_columns(self, j0, j1):
         """(n, j1 - j0): the columns j0 .. j1 - 1 of the basis"""
         out = np.empty((max(int(j1) - int(j0), 1), self.n))
-        check(load().glx_eig_get_columns(self._handle(), int(j0), int(j1), _ptr(out)), 'glx_eig_get_columns')
+        call('glx_eig_get_columns', self._handle(), int(j0), int(j1), _ptr(out))
         return np.ascontiguousarray(out.T)
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_eig_destroy(self._h)
-            self._h = _vp()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def host_group_by_label(labels, k):
@@ -1414,7 +1353,7 @@ def host_group_by_label(labels, k):
     labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
     counts = np.empty(int(k), dtype=np.int64)
     order = np.empty(len(labels), dtype=np.int32)
-    check(load().glx_host_group_by_label(len(labels), _ptr(labels), int(k), _ptr(counts), _ptr(order)), 'glx_host_group_by_label')
+    call('glx_host_group_by_label', len(labels), _ptr(labels), int(k), _ptr(counts), _ptr(order))
     return counts, order
 
 
@@ -1432,7 +1371,7 @@ class incres_options:
         self.opt = _IncresOptions(int(chunk or 0), int(margin or 0), int(next or 0))
 
     def __enter__(self):
-        check(load().glx_incres_set_options(C.byref(self.opt)), 'glx_incres_set_options')
+        call('glx_incres_set_options', C.byref(self.opt))
         return self
 
     def __exit__(self, *exc):
@@ -1440,15 +1379,16 @@ class incres_options:
         return False
 
 
-class Incres:
+class Incres(_Handle):
     """The device half of clustering.incres (glx_incres_*, csrc/incres.hip; the contract is DESIGN.md 4.15): the transition matrix P
     as CSR arrays whose rows keep their STORED order (scipy's `W*D`, unsorted, as it is) and a state of k columns that stays on the
     device.  step(seeds, max_grow) plants the (k, m) seeds, grows until no entry of the state is zero and returns (labels (n) int32,
     sweeps).  A context manager; close() releases the device memory.  GlxError on every refusal of the library, the cap on the sweeps
     included; the object stays usable after it (`last_sweeps` then holds the cap)."""
 
+    _destroy = 'glx_incres_destroy'
+
     def __init__(self, row_ptr, col, val, k, device=None):
-        self._h = _vp()
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
         col = np.ascontiguousarray(col, dtype=np.int32)
         val = np.ascontiguousarray(val, dtype=np.float64)
@@ -1457,12 +1397,7 @@ class Incres:
             raise GlxError('Incres: inconsistent array shapes or sizes')
         self.n, self.k = n, int(k)
         self.last_sweeps = None
-        check(load().glx_incres_create(n, _ptr(row_ptr), _ptr(col), _ptr(val), int(k), _dev(device), C.byref(self._h)), 'glx_incres_create')
-
-    def _handle(self):
-        if not self._h.value:
-            raise GlxError('Incres: the object is closed')
-        return self._h
+        self._open('glx_incres_create', n, _ptr(row_ptr), _ptr(col), _ptr(val), int(k), _dev(device))
 
     def step(self, seeds, max_grow=None, out=None):
         seeds = np.ascontiguousarray(seeds, dtype=np.int32)
@@ -1482,67 +1417,44 @@ class Incres:
     def stats(self):
         """dict: chunk_cap, first_chunk, margin, next_chunk, loops, chunks, enqueued, counted, lanes, record, renumbered, slices"""
         out = (C.c_int64 * 12)()
-        check(load().glx_incres_stats(self._handle(), out), 'glx_incres_stats')
+        call('glx_incres_stats', self._handle(), out)
         names = ('chunk_cap', 'first_chunk', 'margin', 'next_chunk', 'loops', 'chunks', 'enqueued', 'counted', 'lanes', 'record', 'renumbered',
                  'slices')
         return dict(zip(names, (int(v) for v in out)))
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_incres_destroy(self._h)
-            self._h = _vp()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 ACQ_VAR, ACQ_SIGMA, ACQ_MC, ACQ_MCVAR = 0, 1, 2, 3          # the kinds of glx_acq_compute (include/glx_experimental.h)
 ACQ_MAX_M = 256
 
 
-class Acq:
+class Acq(_Handle):
     """The device half of the acquisition functions of active learning (glx_acq_*, csrc/acq.hip; the contract is DESIGN.md 4.19): the
     eigenvectors V (n, M) and the covariance C (M, M) stay on the device.  compute(kind, cand, unc) evaluates the candidates,
     update(query) applies the rank-one steps of a batch in one launch, greedy(kind, cand, b) returns the positions in cand and the
     values that b rounds of evaluate / take the first maximum / update choose, on a scratch copy of C.  A context manager; close()
     releases the device memory.  GlxError on every refusal of the library; the object stays usable after it."""
 
+    _destroy = 'glx_acq_destroy'
+
     def __init__(self, V, C_, gamma2, device=None):
-        self._h = _vp()
         V = np.ascontiguousarray(V, dtype=np.float64)
         C_ = np.ascontiguousarray(C_, dtype=np.float64)
         if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] < 1 or C_.shape != (V.shape[1], V.shape[1]):
             raise GlxError('Acq: V of shape %s and C of shape %s, expected (n, M) and (M, M)' % (V.shape, C_.shape))
         self.n, self.M = V.shape
-        check(load().glx_acq_create(self.n, self.M, _ptr(V), _ptr(C_), float(gamma2), _dev(device), C.byref(self._h)), 'glx_acq_create')
-
-    def _handle(self):
-        if not self._h.value:
-            raise GlxError('Acq: the object is closed')
-        return self._h
+        self._open('glx_acq_create', self.n, self.M, _ptr(V), _ptr(C_), float(gamma2), _dev(device))
 
     def compute(self, kind, cand, unc=None):
         cand = np.ascontiguousarray(cand, dtype=np.int32).ravel()
         if unc is not None:
             unc = _dense(np.asarray(unc).ravel(), np.float64, (len(cand),), 'unc')
         vals = np.empty(len(cand), dtype=np.float64)
-        check(load().glx_acq_compute(self._handle(), int(kind), _ptr(cand), len(cand), _ptr(unc), _ptr(vals)), 'glx_acq_compute')
+        call('glx_acq_compute', self._handle(), int(kind), _ptr(cand), len(cand), _ptr(unc), _ptr(vals))
         return vals
 
     def update(self, query):
         query = np.ascontiguousarray(query, dtype=np.int32).ravel()
-        check(load().glx_acq_update(self._handle(), _ptr(query), len(query)), 'glx_acq_update')
+        call('glx_acq_update', self._handle(), _ptr(query), len(query))
 
     def greedy(self, kind, cand, b):
         """(positions in cand (b) int32, their values (b))"""
@@ -1550,45 +1462,26 @@ class Acq:
         b = int(b)
         queries = np.empty(max(b, 1), dtype=np.int32)
         vals = np.empty(max(b, 1), dtype=np.float64)
-        check(load().glx_acq_greedy(self._handle(), int(kind), _ptr(cand), len(cand), b, _ptr(queries), _ptr(vals)), 'glx_acq_greedy')
+        call('glx_acq_greedy', self._handle(), int(kind), _ptr(cand), len(cand), b, _ptr(queries), _ptr(vals))
         return queries[:b], vals[:b]
 
     def get_c(self):
         out = np.empty((self.M, self.M), dtype=np.float64)
-        check(load().glx_acq_get_c(self._handle(), _ptr(out)), 'glx_acq_get_c')
+        call('glx_acq_get_c', self._handle(), _ptr(out))
         return out
 
     def stats(self):
         """dict: pass_launches, update_launches, greedy_launches, tile_rows, pass_lds, update_lds, n, M"""
         out = (C.c_int64 * 8)()
-        check(load().glx_acq_stats(self._handle(), out), 'glx_acq_stats')
+        call('glx_acq_stats', self._handle(), out)
         names = ('pass_launches', 'update_launches', 'greedy_launches', 'tile_rows', 'pass_lds', 'update_lds', 'n', 'M')
         return dict(zip(names, (int(v) for v in out)))
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_acq_destroy(self._h)
-            self._h = _vp()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def host_row_sums(W):
     """W * ones for a CSR matrix with int32 indices (scipy's csr_matvec order), by the library's host loop."""
     out = np.empty(W.shape[0], dtype=np.float64)
-    check(load().glx_host_row_sums(W.shape[0], _ptr(W.indptr), _ptr(W.data), _ptr(out)), 'glx_host_row_sums')
+    call('glx_host_row_sums', W.shape[0], _ptr(W.indptr), _ptr(W.data), _ptr(out))
     return out
 
 
@@ -1609,8 +1502,8 @@ def host_neg_columns_rows(Lcsc, cols, F, row_scale=None):
     vals = np.empty((max(cap, 1), k), dtype=np.float64)
     cnt = C.c_int64(0)
     scale = None if row_scale is None else np.ascontiguousarray(row_scale, dtype=np.float64)
-    check(load().glx_host_neg_columns_rows(n, _ptr(Lcsc.indptr), _ptr(Lcsc.indices), _ptr(Lcsc.data), len(cols), _ptr(cols), _ptr(F), k,
-                                           _ptr(scale), cap, _ptr(rows), _ptr(vals), C.byref(cnt)), 'glx_host_neg_columns_rows')
+    call('glx_host_neg_columns_rows', n, _ptr(Lcsc.indptr), _ptr(Lcsc.indices), _ptr(Lcsc.data), len(cols), _ptr(cols), _ptr(F), k, _ptr(scale), cap,
+         _ptr(rows), _ptr(vals), C.byref(cnt))
     if cnt.value < 0:
         return None
     return rows[:cnt.value], vals[:cnt.value]
@@ -1620,8 +1513,7 @@ def host_reverse_scale_rows(W, scale):
     """(indices, data) of the matrix whose row i is row i of W times scale[i] with the entries in reverse order."""
     col = np.empty(W.nnz, dtype=np.int32)
     val = np.empty(W.nnz, dtype=np.float64)
-    check(load().glx_host_reverse_scale_rows(W.shape[0], _ptr(W.indptr), _ptr(W.indices), _ptr(W.data), _ptr(scale), _ptr(col), _ptr(val)),
-          'glx_host_reverse_scale_rows')
+    call('glx_host_reverse_scale_rows', W.shape[0], _ptr(W.indptr), _ptr(W.indices), _ptr(W.data), _ptr(scale), _ptr(col), _ptr(val))
     return col, val
 
 
@@ -1660,7 +1552,7 @@ class knn_options:
                                 int(nsplit or 0), -1 if concat is None else int(concat))
 
     def __enter__(self):
-        check(load().glx_knn_set_options(C.byref(self.opt)), 'glx_knn_set_options')
+        call('glx_knn_set_options', C.byref(self.opt))
         return self
 
     def __exit__(self, *exc):
@@ -1709,18 +1601,16 @@ def knn_bruteforce(X, k, similarity='euclidean', device=None, query_range=None, 
     dist = pinned_empty((q1 - q0, k), np.float64)
     if cell_starts is not None:
         cs = np.ascontiguousarray(cell_starts, dtype=np.int64)
-        check(load().glx_knn_cells_range(dev_ptr or _ptr(X), n, d, k, _ptr(cs), len(cs), q0, q1, _ptr(ind), _ptr(dist), _dev(device)),
-              'glx_knn_cells_range')
+        call('glx_knn_cells_range', dev_ptr or _ptr(X), n, d, k, _ptr(cs), len(cs), q0, q1, _ptr(ind), _ptr(dist), _dev(device))
         return ind, dist
     if dev_ptr is not None:
-        check(load().glx_knn_bruteforce_range(dev_ptr, n, d, k, q0, q1, _ptr(ind), _ptr(dist), _dev(device)), 'glx_knn_bruteforce')
+        call('glx_knn_bruteforce_range', dev_ptr, n, d, k, q0, q1, _ptr(ind), _ptr(dist), _dev(device))
         return ind, dist
     m = _knn_cells(n, d, clustered, want_order) if query_range is None else 0
     if m:       # cells formed by the library (same lists; a fraction of the tiles when the data has clusters)
-        check(load().glx_knn_clustered(_ptr(X), n, d, k, m, _ptr(ind), _ptr(dist), _dev(device)), 'glx_knn_clustered')
+        call('glx_knn_clustered', _ptr(X), n, d, k, m, _ptr(ind), _ptr(dist), _dev(device))
         return ind, dist
-    check(load().glx_knn_bruteforce_range(_ptr(X), n, d, k, q0, q1, _ptr(ind), _ptr(dist), _dev(device)),
-          'glx_knn_bruteforce')
+    call('glx_knn_bruteforce_range', _ptr(X), n, d, k, q0, q1, _ptr(ind), _ptr(dist), _dev(device))
     return ind, dist
 
 
@@ -1732,29 +1622,29 @@ KNN_K_LISTS = 60      # k (self included) of the list-returning searches: knn_br
 KNN_K_MAX = 1024      # k (self included) of KnnResult (glx_knn_search)
 
 
-class KnnResult:
+class KnnResult(_Handle):
     """A finished full search whose lists live on the device (glx_knn_search): `to_csr` builds the weight matrix from them
     without a host round trip, `lists()` copies them out, `order()` is the cell order the search worked out (or None).
     k (self included) from 1 to min(n, KNN_K_MAX); above KNN_K_LISTS the search takes its wide plan (longer and more
     candidate lists, processed in chunks of queries), whose lists are the same exact lists."""
 
+    _destroy = 'glx_knn_result_destroy'
+
     def __init__(self, X, k, similarity='euclidean', device=None, clustered=None, want_order=False):
         X = _knn_input(X, similarity)
         n, d = X.shape
         self.n, self.k, self.device = n, int(k), _dev(device)
-        self._h = _vp()
-        check(load().glx_knn_search(_ptr(X), n, d, int(k), _knn_cells(n, d, clustered, want_order), self.device, C.byref(self._h)),
-              'glx_knn_search')
+        self._open('glx_knn_search', _ptr(X), n, d, int(k), _knn_cells(n, d, clustered, want_order), self.device)
 
     def lists(self):
         ind = pinned_empty((self.n, self.k), np.int64)
         dist = pinned_empty((self.n, self.k), np.float64)
-        check(load().glx_knn_result_lists(self._h, _ptr(ind), _ptr(dist)), 'glx_knn_result_lists')
+        call('glx_knn_result_lists', self._handle(), _ptr(ind), _ptr(dist))
         return ind, dist
 
     def order(self):
         perm = pinned_empty((self.n,), np.int32)         # (a device-to-host copy into fresh pageable memory takes milliseconds the first time)
-        if load().glx_knn_result_order(self._h, _ptr(perm)) != 0:
+        if load().glx_knn_result_order(self._handle(), _ptr(perm)) != 0:
             return None
         return perm
 
@@ -1768,30 +1658,19 @@ class KnnResult:
         col_buf = pinned_empty((cap,), np.int32) if pinned else np.empty(cap, np.int32)
         val_buf = pinned_empty((cap,), np.float64) if pinned else np.empty(cap, np.float64)
         nnz = C.c_int64(0)
-        check(load().glx_knn_result_to_csr(self._h, int(k), _KERNEL_ID[kernel], int(sym), _ptr(w), cap, _ptr(indptr), _ptr(col_buf),
-                                           _ptr(val_buf), C.byref(nnz)), 'glx_knn_result_to_csr')
+        call('glx_knn_result_to_csr', self._handle(), int(k), _KERNEL_ID[kernel], int(sym), _ptr(w), cap, _ptr(indptr), _ptr(col_buf), _ptr(val_buf),
+             C.byref(nnz))
         W = sparse.csr_matrix((val_buf[:nnz.value], col_buf[:nnz.value], indptr), shape=(n, n))
         W.has_sorted_indices = True
         W.has_canonical_format = True
         return W
 
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_knn_result_destroy(self._h)
-            self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BallResult:
+class BallResult(_Handle):
     """A finished radius search whose structure lives on the device (glx_ball_search): `to_csr` weighs it and returns the
     scipy CSR matrix, `structure()` returns it with the distances the weights see instead (for kernels evaluated on the host)."""
+
+    _destroy = 'glx_ball_result_destroy'
 
     def __init__(self, X, epsilon, features=None, device=None):
         X = _dense(X, np.float64, name='data')
@@ -1800,11 +1679,9 @@ class BallResult:
         if F is not None and (F.ndim != 2 or F.shape[0] != n):
             raise GlxError('features have shape %s, expected (%d, m)' % (F.shape, n))
         self.n, self.device, self.has_features = n, _dev(device), F is not None
-        self._h = _vp()
-        check(load().glx_ball_search(_ptr(X), n, d, float(epsilon), _ptr(F), 0 if F is None else F.shape[1], self.device,
-                                     C.byref(self._h)), 'glx_ball_search')
+        self._open('glx_ball_search', _ptr(X), n, d, float(epsilon), _ptr(F), 0 if F is None else F.shape[1], self.device)
         nnz = C.c_int64(0)
-        check(load().glx_ball_result_nnz(self._h, C.byref(nnz)), 'glx_ball_result_nnz')
+        call('glx_ball_result_nnz', self._handle(), C.byref(nnz))
         self.nnz = nnz.value
 
     def _arrays(self, specs):
@@ -1824,8 +1701,8 @@ class BallResult:
         """The weight matrix of one of the device kernels ('uniform', 'gaussian', 'distance', 'singular'), zero weights dropped."""
         indptr, col, val = self._arrays([((self.n + 1,), np.int32), ((self.nnz,), np.int32), ((self.nnz,), np.float64)])
         m = C.c_int64(0)
-        check(load().glx_ball_result_to_csr(self._h, _KERNEL_ID[kernel], float(epsilon_f), _ptr(indptr), _ptr(col), _ptr(val), None, None,
-                                            C.byref(m)), 'glx_ball_result_to_csr')
+        call('glx_ball_result_to_csr', self._handle(), _KERNEL_ID[kernel], float(epsilon_f), _ptr(indptr), _ptr(col), _ptr(val), None, None,
+             C.byref(m))
         return self._csr(indptr, col, val, m.value)
 
     def structure(self):
@@ -1838,27 +1715,13 @@ class BallResult:
         indptr, col, dists = arrs[:3]
         fd = arrs[3] if self.has_features else None
         m = C.c_int64(0)
-        check(load().glx_ball_result_to_csr(self._h, _KERNEL_ID['given'], 1.0, _ptr(indptr), _ptr(col), None, _ptr(dists), _ptr(fd),
-                                            C.byref(m)), 'glx_ball_result_to_csr')
+        call('glx_ball_result_to_csr', self._handle(), _KERNEL_ID['given'], 1.0, _ptr(indptr), _ptr(col), None, _ptr(dists), _ptr(fd), C.byref(m))
         return indptr, col[:m.value], dists[:m.value], (None if fd is None else fd[:m.value])
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            lib = load(required=False)
-            if lib is not None:
-                lib.glx_ball_result_destroy(self._h)
-            self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def ball_stats():
     out = (C.c_double * 8)()
-    check(load().glx_ball_stats(out), 'glx_ball_stats')
+    call('glx_ball_stats', out)
     return dict(pairs_tested=out[0], pairs_accepted=out[1], cells=int(out[2]), grid_ms=out[3], count_ms=out[4], fill_ms=out[5],
                 sort_ms=out[6], weights_ms=out[7])
 
@@ -1867,7 +1730,7 @@ def exp_cr(x, device=None):
     """exp(x), correctly rounded, evaluated on the device (glx_exp_cr)."""
     x = np.ascontiguousarray(x, dtype=np.float64)
     out = np.empty_like(x)
-    check(load().glx_exp_cr(_ptr(x), _ptr(out), x.size, _dev(device)), 'glx_exp_cr')
+    call('glx_exp_cr', _ptr(x), _ptr(out), x.size, _dev(device))
     return out
 
 
@@ -1888,13 +1751,13 @@ def knn_to_csr(knn_ind, knn_dist, k, kernel='gaussian', sym=1, weights=None, dev
         indptr = pinned_empty((n + 1,), np.int32)
         col_buf = pinned_empty((cap,), np.int32)
         val_buf = pinned_empty((cap,), np.float64)
-        check(lib.glx_knn_to_csr_into(_ptr(ind), _ptr(dist), _ptr(w), n, kk, int(k), _KERNEL_ID[kernel], int(sym), cap, _ptr(indptr),
-                                      _ptr(col_buf), _ptr(val_buf), C.byref(nnz), _dev(device)), 'glx_knn_to_csr_into')
+        call('glx_knn_to_csr_into', _ptr(ind), _ptr(dist), _ptr(w), n, kk, int(k), _KERNEL_ID[kernel], int(sym), cap, _ptr(indptr), _ptr(col_buf),
+             _ptr(val_buf), C.byref(nnz), _dev(device))
         indices, data = col_buf[:nnz.value], val_buf[:nnz.value]
     else:
         rp, ci, va = _vp(), _vp(), _vp()
-        check(lib.glx_knn_to_csr(_ptr(ind), _ptr(dist), _ptr(w), n, kk, int(k), _KERNEL_ID[kernel], int(sym), C.byref(rp),
-                                 C.byref(ci), C.byref(va), C.byref(nnz), _dev(device)), 'glx_knn_to_csr')
+        call('glx_knn_to_csr', _ptr(ind), _ptr(dist), _ptr(w), n, kk, int(k), _KERNEL_ID[kernel], int(sym), C.byref(rp), C.byref(ci), C.byref(va),
+             C.byref(nnz), _dev(device))
         try:
             m = nnz.value
             indptr = np.ctypeslib.as_array(C.cast(rp, _i32p), shape=(n + 1,)).copy()
@@ -1926,8 +1789,8 @@ def knn_rows_to_csr(J_own, w_own, n_cols, row_base, rev_row, rev_src, rev_pos, r
     col = np.empty(max(cap, 1), dtype=np.int32)
     val = np.empty(max(cap, 1), dtype=np.float64)
     nnz = C.c_int64(0)
-    check(load().glx_knn_rows_to_csr(_ptr(J), _ptr(w), m, k, int(n_cols), int(row_base), _ptr(rr), _ptr(rs), _ptr(rp), _ptr(rw), len(rr), int(sym),
-                                     cap, _ptr(indptr), _ptr(col), _ptr(val), C.byref(nnz), _dev(device)), 'glx_knn_rows_to_csr')
+    call('glx_knn_rows_to_csr', _ptr(J), _ptr(w), m, k, int(n_cols), int(row_base), _ptr(rr), _ptr(rs), _ptr(rp), _ptr(rw), len(rr), int(sym), cap,
+         _ptr(indptr), _ptr(col), _ptr(val), C.byref(nnz), _dev(device))
     W = sparse.csr_matrix((val[:nnz.value].copy(), col[:nnz.value].copy(), indptr), shape=(m, int(n_cols)))
     W.has_sorted_indices = True
     W.has_canonical_format = True
@@ -1940,7 +1803,7 @@ def host_locality_order(indptr, indices, col_lo=0):
     indices = np.ascontiguousarray(indices, dtype=np.int32)
     n = len(indptr) - 1
     perm = np.empty(n, dtype=np.int32)
-    check(load().glx_host_locality_order(n, _ptr(indptr), _ptr(indices), int(col_lo), _ptr(perm)), 'glx_host_locality_order')
+    call('glx_host_locality_order', n, _ptr(indptr), _ptr(indices), int(col_lo), _ptr(perm))
     return perm
 
 
@@ -1953,7 +1816,7 @@ def host_permute_rows(A, perm):
     perm = np.ascontiguousarray(perm, dtype=np.int64)
     n = len(indptr) - 1
     ip, ix, dv = np.empty(n + 1, dtype=np.int32), np.empty(len(indices), dtype=np.int32), np.empty(len(data), dtype=np.float64)
-    check(load().glx_host_permute_rows(n, _ptr(indptr), _ptr(indices), _ptr(data), _ptr(perm), _ptr(ip), _ptr(ix), _ptr(dv)), 'glx_host_permute_rows')
+    call('glx_host_permute_rows', n, _ptr(indptr), _ptr(indices), _ptr(data), _ptr(perm), _ptr(ip), _ptr(ix), _ptr(dv))
     out = sparse.csr_matrix((dv, ix, ip), shape=A.shape)
     out.has_sorted_indices = A.has_sorted_indices
     return out
@@ -1961,7 +1824,7 @@ def host_permute_rows(A, perm):
 
 def knn_stats():
     out = (C.c_double * 16)()
-    check(load().glx_knn_stats(out), 'glx_knn_stats')
+    call('glx_knn_stats', out)
     return dict(tile_ms=out[0], rerank_ms=out[1], fallback_rows=out[2], total_ms=out[3], fallback_ms=out[4],
                 dpa=out[5], nsplit=out[6], KP=abs(out[7]), filter='bf16x3' if out[7] < 0 else 'f32', escalated_rows=out[8],
                 concatenated=int(out[9]), seed_sample=int(out[10]), visited_share=out[11], cells=int(out[12]),

@@ -534,7 +534,7 @@ class HipOps:
             g = _hip.DeviceGraph(sub, dtype=self.dtype, device=device, shape=(hi - lo, plan.P_local.shape[1]),
                                  keep_order=True)   # records stay in the partition's order
             n = _hip.C.c_int64(0)
-            _hip.check(_hip.load().glx_graph_slots(g._h, C, 1, _hip.C.byref(n)), 'glx_graph_slots')
+            _hip.call('glx_graph_slots', g._h, C, 1, _hip.C.byref(n))
             self.parts.append(dict(graph=g, lo=lo, hi=hi, flags=torch.zeros(max(n.value, 1), dtype=torch.uint8, device=self.device),
                                    err=torch.zeros(64, dtype=torch.int64, device=self.device)))
         self.rec_bytes = self.lay['rec_bytes']
@@ -558,29 +558,24 @@ class HipOps:
     def pack(self, dense, w, rows):
         """(rows, C) dense [or None = zeros] + optional (rows,) fp64 stop values -> records."""
         rec = self.new_state(rows)
-        lib = self._hip.load()
         d = None if dense is None else self.to_device(dense, self.tdtype)
         wt = None if w is None else self.to_device(w, self.torch.float64)
-        self._hip.check(lib.glx_pack_records_dev(None if d is None else d.data_ptr(), rec.data_ptr(), rows, self.C,
-                                                  self._hip._dt(self.dtype), 1, None if wt is None else wt.data_ptr(),
-                                                  self._stream()), 'glx_pack_records_dev')
+        self._hip.call('glx_pack_records_dev', None if d is None else d.data_ptr(), rec.data_ptr(), rows, self.C, self._hip._dt(self.dtype), 1,
+                       None if wt is None else wt.data_ptr(), self._stream())
         self.torch.cuda.current_stream(self.device).synchronize()   # d / wt die here
         return rec
 
     def unpack(self, rec, rows):
         out = self.torch.empty((rows, self.C), dtype=self.tdtype, device=self.device)
-        self._hip.check(self._hip.load().glx_unpack_records_dev(rec.data_ptr(), out.data_ptr(), rows, self.C,
-                                                                 self._hip._dt(self.dtype), 1, self._stream()),
-                        'glx_unpack_records_dev')
+        self._hip.call('glx_unpack_records_dev', rec.data_ptr(), out.data_ptr(), rows, self.C, self._hip._dt(self.dtype), 1, self._stream())
         return out.cpu().numpy()
 
     def set_bias(self, bias_rec):
         self.bias = bias_rec
         for part in self.parts:
             if part is not None:
-                self._hip.check(self._hip.load().glx_bias_flags_dev(
-                    part['graph']._h, self.C, 1, bias_rec.data_ptr() + part['lo'] * self.rec_bytes, part['flags'].data_ptr(),
-                    self._stream()), 'glx_bias_flags_dev')
+                self._hip.call('glx_bias_flags_dev', part['graph']._h, self.C, 1, bias_rec.data_ptr() + part['lo'] * self.rec_bytes,
+                               part['flags'].data_ptr(), self._stream())
 
     def set_stop_vectors(self, deg, vinf):
         self.deg = self.to_device(deg, self.torch.float64)
@@ -594,10 +589,9 @@ class HipOps:
         lo = part['lo']
         if want_err:
             part['err'].zero_()
-        self._hip.check(self._hip.load().glx_sweep_step_dev(
-            part['graph']._h, self.C, 1, xin.data_ptr(), xout.data_ptr() + (self.own_off + lo) * self.rec_bytes,
-            self.bias.data_ptr() + lo * self.rec_bytes, part['flags'].data_ptr(), self.deg.data_ptr() + lo * 8,
-            self.vinf.data_ptr() + lo * 8, part['err'].data_ptr() if want_err else None, self._stream()), 'glx_sweep_step_dev')
+        self._hip.call('glx_sweep_step_dev', part['graph']._h, self.C, 1, xin.data_ptr(), xout.data_ptr() + (self.own_off + lo) * self.rec_bytes,
+                       self.bias.data_ptr() + lo * self.rec_bytes, part['flags'].data_ptr(), self.deg.data_ptr() + lo * 8,
+                       self.vinf.data_ptr() + lo * 8, part['err'].data_ptr() if want_err else None, self._stream())
         if want_err:   # fp64 bit patterns of non-negative values order like the values
             return part['err'].max().view(1).view(self.torch.float64)
         return None
@@ -1133,36 +1127,34 @@ class CgHipOps:
         rec = self.torch.zeros((rows, self.ld), dtype=self.tdtype, device=self.device)
         if dense_own is not None:
             d = self.to_device(dense_own, self.tdtype)
-            self._hip.check(self._hip.load().glx_pack_records_dev(d.data_ptr(), rec.data_ptr(), dense_own.shape[0], self.C,
-                                                                  self._hip._dt(self.dtype), 0, None, self._stream()), 'glx_pack_records_dev')
+            self._hip.call('glx_pack_records_dev', d.data_ptr(), rec.data_ptr(), dense_own.shape[0], self.C, self._hip._dt(self.dtype), 0, None,
+                           self._stream())
             self.torch.cuda.current_stream(self.device).synchronize()
         return rec
 
     def spmm(self, p_loc, Ap):
-        self._hip.check(self._hip.load().glx_sweep_step_dev(self.graph._h, self.C, 0, p_loc.data_ptr(), Ap.data_ptr(), None, None, None, None,
-                                                            None, self._stream()), 'glx_sweep_step_dev')
+        self._hip.call('glx_sweep_step_dev', self.graph._h, self.C, 0, p_loc.data_ptr(), Ap.data_ptr(), None, None, None, None, None, self._stream())
 
     def dots(self, a, b):
-        self._hip.check(self._hip.load().glx_rec_dots_dev(a.data_ptr(), b.data_ptr(), self.plan.n_own, self.C, self._hip._dt(self.dtype), 0,
-                                                          self.scratch.data_ptr(), self.dot_out.data_ptr(), self._stream()), 'glx_rec_dots_dev')
+        self._hip.call('glx_rec_dots_dev', a.data_ptr(), b.data_ptr(), self.plan.n_own, self.C, self._hip._dt(self.dtype), 0, self.scratch.data_ptr(),
+                       self.dot_out.data_ptr(), self._stream())
         return self.dot_out[:self.C].cpu().numpy().copy()
 
     def axpy2(self, x, r, p_loc, Ap, alpha):
         al = self.to_device(np.ascontiguousarray(alpha, dtype=np.float64))
-        self._hip.check(self._hip.load().glx_rec_axpy2_dev(x.data_ptr(), r.data_ptr(), p_loc.data_ptr(), Ap.data_ptr(), al.data_ptr(),
-                                                           self.plan.n_own, self.C, self._hip._dt(self.dtype), 0, self._stream()), 'glx_rec_axpy2_dev')
+        self._hip.call('glx_rec_axpy2_dev', x.data_ptr(), r.data_ptr(), p_loc.data_ptr(), Ap.data_ptr(), al.data_ptr(), self.plan.n_own, self.C,
+                       self._hip._dt(self.dtype), 0, self._stream())
         self.torch.cuda.current_stream(self.device).synchronize()      # `al` dies here
 
     def xpby(self, p_loc, r, beta):
         be = self.to_device(np.ascontiguousarray(beta, dtype=np.float64))
-        self._hip.check(self._hip.load().glx_rec_xpby_dev(p_loc.data_ptr(), r.data_ptr(), be.data_ptr(), self.plan.n_own, self.C,
-                                                          self._hip._dt(self.dtype), 0, self._stream()), 'glx_rec_xpby_dev')
+        self._hip.call('glx_rec_xpby_dev', p_loc.data_ptr(), r.data_ptr(), be.data_ptr(), self.plan.n_own, self.C, self._hip._dt(self.dtype), 0,
+                       self._stream())
         self.torch.cuda.current_stream(self.device).synchronize()
 
     def to_host(self, x):
         out = self.torch.empty((self.plan.n_own, self.C), dtype=self.tdtype, device=self.device)
-        self._hip.check(self._hip.load().glx_unpack_records_dev(x.data_ptr(), out.data_ptr(), self.plan.n_own, self.C, self._hip._dt(self.dtype), 0,
-                                                                self._stream()), 'glx_unpack_records_dev')
+        self._hip.call('glx_unpack_records_dev', x.data_ptr(), out.data_ptr(), self.plan.n_own, self.C, self._hip._dt(self.dtype), 0, self._stream())
         return out.cpu().numpy()
 
     def close(self):
