@@ -157,6 +157,8 @@ _SIGNATURES = {
     'glx_components': [C.c_int64, C.c_int64, _vp, _vp, _vp, _i64p, _f64p, C.c_int],
     'glx_components_set_wave_row': [C.c_int],
     'glx_components_plan': [_i64p],
+    'glx_boundary_stat': [C.c_int64, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _f64p, C.c_int],
+    'glx_boundary_stat_set_wave_row': [C.c_int],
     'glx_lip_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_double,
                         _vp, _vp, _vp, _vp, C.c_int, C.c_int],
     'glx_slp_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
@@ -1163,6 +1165,45 @@ def components_plan():
     out = (C.c_int64 * 4)()
     call('glx_components_plan', out)
     return tuple(int(v) for v in out)
+
+
+BSTAT_SECOND_ORDER, BSTAT_CUTOFF = 1, 2          # flags of glx_boundary_stat (include/glx_experimental.h)
+# of the last call: launches, rows of the short class, rows on a wavefront, rows of the largest length, host milliseconds of the
+# checks, uploads, kernels, downloads
+boundary_stat_last = None
+
+
+def boundary_stat(X, indptr, indices, second_order=True, cutoff=True, J=None, device=None):
+    """The boundary statistic over a canonical CSR pattern with unit weights (glx_boundary_stat, csrc/bstat.hip).  X (n, d) float64;
+    J (n, k) the neighbour lists of the kNN mode, None: the radius mode.  Returns (T (n,), nu (n, d)) float64.  Malformed arrays, an
+    empty row and a normal of norm zero are refused with GlxError."""
+    global boundary_stat_last
+    X = _dense(X, np.float64, name='X')
+    if X.ndim != 2:
+        raise GlxError('boundary_stat: X must be (n, d), got shape %s' % (X.shape,))
+    n, d = X.shape
+    indptr = int32_index_array(indptr, 'indptr')
+    indices = int32_index_array(indices, 'indices')
+    if indptr.ndim != 1 or indices.ndim != 1 or len(indptr) != n + 1:
+        raise GlxError('boundary_stat: indptr has %s entries for n = %d' % (indptr.shape, n))
+    k = 0
+    if J is not None:
+        J = int32_index_array(J, 'J')
+        if J.ndim != 2 or J.shape[0] != n or J.shape[1] < 1:
+            raise GlxError('boundary_stat: J has shape %s for n = %d' % (J.shape, n))
+        k = J.shape[1]
+    T, nu = np.empty(n), np.empty((n, d))
+    stats = (C.c_double * 8)()
+    flags = (BSTAT_SECOND_ORDER if second_order else 0) | (BSTAT_CUTOFF if cutoff else 0)
+    call('glx_boundary_stat', n, d, _ptr(X), len(indices), _ptr(indptr), _ptr(indices), k, _ptr(J), flags, _ptr(T), _ptr(nu), stats,
+         _dev(device))
+    boundary_stat_last = tuple(stats)
+    return T, nu
+
+
+def boundary_stat_set_wave_row(min_members=0):
+    """plan override of the calling thread for measurements: rows of at least `min_members` members take a wavefront (0: the library's)"""
+    call('glx_boundary_stat_set_wave_row', int(min_members))
 
 
 def lip_iterate(n, nbr, row, W, ind, val, weighted, alpha, beta, T, tol, device=None, want_errors=False, small_level=-1):

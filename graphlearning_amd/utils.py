@@ -20,6 +20,73 @@ def labels_to_onehot(labels, k, standardize=False):
     return onehot
 
 
+def boundary_statistic(X, r, knn=False, return_normals=False, second_order=True, cutoff=True, knn_data=None, device=None):
+    """Boundary test statistic of a point cloud (reference utils.py:18-114, plus `device`; J. Calder, S. Park, D. Slepcev, Boundary
+    Estimation from Point Clouds, arXiv:2111.03217): T (n,) float64, small at the boundary; with return_normals=True (T, nu), nu (n, d)
+    the estimated unit normals.
+
+    Radius mode: the ball graph of weightmatrix.epsilon_ball(X, r, kernel='uniform'); kNN mode (knn=True, r = k neighbours with self
+    counted): the lists of weightmatrix.knnsearch(X, k), or `knn_data`, and the graph weightmatrix.knn(X, k, kernel='uniform',
+    symmetrize=False, knn_data=...).  Everything behind the graph is one device call (csrc/bstat.hip): the normals equal the
+    reference's bit for bit, T as numbers (a zero is +0.0; the reference leaves its sign to np.max over a masked product).
+    Where the reference's second search and this walk over the ball graph part ways, the call refuses with ValueError before any
+    device call: a vertex with no neighbour (the reference divides 0 by 0 and spreads the NaN), non-finite X, a negative or NaN
+    radius, a k that is no integer in 2 .. min(n, 1024), knn_data with fewer than k or more than min(n, 1024) columns, other row
+    counts or an index out of range, a duplicate in a neighbour list (a weight other than 1).  knn_data wider than k is used as the
+    reference uses it: the graph from its first k + 1 columns, the maximum over all of them.  A normal of norm zero (a lattice; the reference returns NaN there
+    and around it) raises GlxError naming the vertex.  Radius-mode membership is the ball graph's sq <= r*r; the reference masks its
+    lists with sqrt(sq) <= r, which can differ for a pair within rounding of the radius."""
+    from . import weightmatrix           # (weightmatrix imports utils)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError('boundary_statistic: X must be (n, d) with n, d >= 1 (got shape %s)' % (X.shape,))
+    if not np.isfinite(X).all():
+        raise ValueError('boundary_statistic: X must be finite')
+    n = X.shape[0]
+    J = None
+    if knn:
+        if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)):
+            if not (isinstance(r, (float, np.floating)) and float(r).is_integer()):
+                raise ValueError('boundary_statistic: with knn=True r is the number of neighbours, an integer (got %r)' % (r,))
+        k = int(r)
+        if k < 2 or k > min(n, 1024):
+            raise ValueError('boundary_statistic: k = %d outside 2 .. min(n, 1024) = %d' % (k, min(n, 1024)))
+        if knn_data is not None:
+            J, D = np.asarray(knn_data[0]), np.asarray(knn_data[1])
+            if J.ndim != 2 or D.ndim != 2 or J.shape != D.shape or J.shape[0] != n or not k <= J.shape[1] <= min(n, 1024):
+                raise ValueError('boundary_statistic: knn_data must be two (n, k .. min(n, 1024)) arrays (got %s and %s for n = %d, k = %d)'
+                                 % (J.shape, D.shape, n, k))
+            if J.dtype.kind not in 'iu':
+                raise ValueError('boundary_statistic: knn_data indices must be integers, not %s' % J.dtype)
+            if J.size and (int(J.min()) < 0 or int(J.max()) >= n):
+                raise ValueError('boundary_statistic: knn_data holds an index outside 0 .. n - 1')
+            # as in the reference, wider lists are used in full: weightmatrix.knn counts self on top of k and builds the graph
+            # from the first k + 1 columns, the maximum runs over every column handed in
+            Js = np.sort(J[:, :k + 1], axis=1)
+            if (Js[:, 1:] == Js[:, :-1]).any():
+                raise ValueError('boundary_statistic: a neighbour list of knn_data names a vertex twice (a weight other than 1)')
+        else:
+            J, D = weightmatrix.knnsearch(X, k, device=device)
+        W = weightmatrix.knn(X, k, kernel='uniform', symmetrize=False, knn_data=(J, D), device=device)
+        J = np.ascontiguousarray(J, dtype=np.int32)
+    else:
+        if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, float, np.integer, np.floating)) or not r >= 0:
+            raise ValueError('boundary_statistic: the radius must be a number, not negative or NaN (got %r)' % (r,))
+        W = weightmatrix.epsilon_ball(X, r, kernel='uniform', device=device)
+    W = sparse.csr_matrix(W)
+    if not W.has_canonical_format:
+        W.sum_duplicates()
+    if (W.data != 1).any():
+        raise ValueError('boundary_statistic: a weight other than 1 (a neighbour list names a vertex twice)')
+    if (np.diff(W.indptr) == 0).any():
+        raise ValueError('boundary_statistic: vertex %d has no neighbour (the reference divides 0 by 0 there)'
+                         % int(np.flatnonzero(np.diff(W.indptr) == 0)[0]))
+    T, nu = _hip.boundary_stat(X, W.indptr, W.indices, second_order=bool(second_order), cutoff=bool(cutoff), J=J, device=device)
+    if return_normals:
+        return T, nu
+    return T
+
+
 def class_priors(labels):
     """Fraction of data in each class, negative labels ignored (reference utils.py:117-142)."""
     labels = np.asarray(labels)

@@ -419,6 +419,28 @@ int glx_acq_get_c(glx_acq* h, double* C_out);
 int glx_acq_stats(glx_acq* h, int64_t* out);
 int glx_acq_destroy(glx_acq* h);
 
+/* ---- boundary test of a point cloud: utils.boundary_statistic (csrc/bstat.hip, csrc/bstat_plan.h) ----------------------------------
+ * The boundary statistic of Calder, Park and Slepcev (reference utils.py:18-114) over the rows of a canonical CSR pattern whose
+ * weights are all 1 (only the pattern arrives): the ball graph of weightmatrix.epsilon_ball in the radius mode, the directed kNN graph
+ * of weightmatrix.knn(symmetrize=False) in the kNN mode.  The arithmetic, operation by operation, heads csrc/bstat_plan.h; the
+ * normals equal the reference's bit for bit, the statistic as numbers (a zero is +0.0).
+ * X (n, d) row-major; indptr (n + 1) / indices (nnz) the pattern; J (n, k) the neighbour lists of the kNN mode (self included) or NULL
+ * with k = 0: the radius mode, whose lists are the rows of the pattern, a row of the largest length L without its farthest entry and
+ * every row of fewer than L - 1 entries with a 0 among its terms (a row of exactly L - 1 entries: its entries, no 0).  flags: GLX_BSTAT_SECOND_ORDER | GLX_BSTAT_CUTOFF.
+ * T (n) <- the statistic, nu (n, d) <- the unit normals.  stats_out[8] (or NULL): launches, rows of the short class, rows that took a
+ * wavefront, rows of the largest length (radius mode), host milliseconds of the checks, the uploads, the kernels and the downloads.
+ * All pointers are host pointers.  GLX_EINVAL, before anything is launched: a null argument, sizes below 1 or above 2^31 - 1, k above
+ * min(n, 1024), row pointers that do not run from 0 to nnz ascending, a column or list index outside [0, n), a row whose columns
+ * are not strictly ascending, an empty row.  GLX_EINVAL behind the kernels: a vertex whose raw normal has norm zero or not finite (the
+ * message names the lowest such vertex; T and nu are left untouched).
+ * glx_boundary_stat_set_wave_row: a plan override of the calling thread for measurements -- rows of at least that many members take
+ * a wavefront, shorter ones a group of 16 lanes (0: the library's BSTAT_WAVE_ROW).  No result depends on it. */
+#define GLX_BSTAT_SECOND_ORDER 1
+#define GLX_BSTAT_CUTOFF 2
+int glx_boundary_stat(int64_t n, int d, const double* X, int64_t nnz, const int32_t* indptr, const int32_t* indices, int k,
+                      const int32_t* J, int flags, double* T, double* nu, double* stats_out, int device);
+int glx_boundary_stat_set_wave_row(int min_members);
+
 #ifdef __cplusplus
 }
 #endif
