@@ -508,9 +508,10 @@ int glx_sweep_capture(SweepCore* c, const std::function<int()>& enqueue, hipGrap
 // head of a run: the stop row the head's last sweep writes starts from zero and, for min_iter = 0, row 0 comes from the mirror
 // (glx_sweep_put_err0 fills it before the head is launched or replayed).  Capturable.
 void glx_sweep_put_err0(SweepCore* c, const double* err0);
-int glx_sweep_head_rows(SweepCore* c);
+// start_iterate (the single form): the same kernel also writes buf[0] = (u = 0, stop value w0 through perm), and cur = 0.
+int glx_sweep_head_rows(SweepCore* c, bool start_iterate = false);
 // the conditional sweeps behind the head, for the groups `c->walk` was started with (launch(t) enqueues sweep t), and the end of the
-// run: ev1, synchronise, device time since ev0.  See sweep_core.hip.
+// run: ev1, synchronise (once, for a run that stops at its head), device time since ev0.  See sweep_core.hip.
 int glx_sweep_tail(SweepCore* c, const std::function<int(int)>& launch, float* device_ms_out);
 int glx_sweep_stop_values_core(const SweepCore* c, int b, int64_t cap, double* vals, int* first, int* count);
 // where the (n, C) iterate goes for the label decision: fp64 straight into the projector's scores, float32 through `dense`

@@ -241,11 +241,10 @@ extern "C" int glx_sweep_set_problem_rows(glx_sweep* s, int64_t m, const int64_t
 
 static int enqueue_iterate(glx_sweep* s, int iters);
 
-// reset state + the min_iter unconditional sweeps; identical every run -> capturable
+// reset state (one kernel: u = 0 (ssl.py:645), w = w0, the head's stop row cleared) + the min_iter unconditional sweeps; identical
+// every run -> capturable
 static int enqueue_head(glx_sweep* s) {
-  GLX_UP(glx_sweep_head_rows(s));
-  s->cur = 0;
-  GLX_UP(glx_pack_records(nullptr, s->buf[0], s->n_cols, s->L, s->P->dtype, s->w0, s->stream, s->P->d_perm));   // u = 0 (ssl.py:645), w = w0
+  GLX_UP(glx_sweep_head_rows(s, true));
   for (int t = 0; t < s->walk.head; ++t) GLX_UP(glx_sweep_launch(s, t, true, 0));
   return GLX_OK;
 }
@@ -261,6 +260,10 @@ extern "C" int glx_sweep_run(glx_sweep* s, int* T_out, float* device_ms_out) {
   // its destruction cost 1.1-1.4 ms against 0.35 ms of launching the same 50 sweeps one by one (they run behind each other either way:
   // 0.62 ms of device time; profiles/r06_fresh_path.txt).  The first run of a sweep object therefore launches eagerly; the graph is captured
   // on the second run and replayed from then on.  Same kernels, same order: the iterates do not depend on the form.
+  // The graph is the start kernel (sweep_start_kernel, sweep_core.hip: the whole reset in one node) and the min_iter sweeps -- 51 kernel
+  // nodes at config 2 -- plus, for min_iter = 0 only, the upload of stop row 0 behind the start kernel.  Launching the start kernel and
+  // sweep 0 directly and replaying sweeps 1 .. only ("primed replay") was measured and is not done: 0.618 against 0.616 ms per step
+  // (profiles/sweep_head.txt).
   const bool replay = s->use_graph && (s->runs > 0 || s->head_exec);
   ++s->runs;
   if (replay) {

@@ -199,13 +199,47 @@ void glx_sweep_put_err0(SweepCore* c, const double* err0) {
   for (int b = 0; b < c->B; ++b) c->h_err[(size_t)b * c->shards] = stop_bits(err0[b]);
 }
 
+// The start of a run of the single form in ONE kernel (before: glx_zero_async + pack_kernel + write_w_kernel, 14.7 us of kernels per
+// step at config 2, profiles/sweep_head.txt): every record of the start iterate written whole in 16-byte pieces -- u = 0
+// (ssl.py:645) and the padding as zeros, the fp64 stop value w[perm[row]] in the first half of piece woff / 16 -- and, by the first
+// workgroup, the `nerr` words of the stop row the head's last sweep does its atomic maxima into.  The bytes are those of
+// glx_pack_records(nullptr, ..., w, perm), in either state dtype.
+__global__ __launch_bounds__(256) void sweep_start_kernel(ulonglong2* __restrict__ rec, int64_t npieces, int pieces_per_rec, int w_piece,
+                                                          const double* __restrict__ w, const int32_t* __restrict__ perm,
+                                                          unsigned long long* __restrict__ err_row, int nerr) {
+  if (blockIdx.x == 0)
+    for (int j = threadIdx.x; j < nerr; j += 256) err_row[j] = 0ull;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= npieces) return;
+  const int64_t row = i / pieces_per_rec;
+  ulonglong2 v = make_ulonglong2(0ull, 0ull);
+  if ((int)(i - row * pieces_per_rec) == w_piece) v.x = (unsigned long long)__double_as_longlong(w[perm ? perm[row] : row]);
+  rec[i] = v;
+}
+
 // The stop values the head's sweeps write are row min_iter (written by sweep min_iter - 1) and, for min_iter = 0, row 0; the rows of
 // a tail chunk are cleared in front of that chunk (glx_sweep_tail) -- not all max_iter + 1 rows on every run (512 KB, 6.6 us of a
-// 620 us step at config 2).
-int glx_sweep_head_rows(SweepCore* c) {
-  const size_t er = c->err_row();
-  // (a kernel, not a memset node: this sequence is captured and replayed -- glx_zero_async, glx_internal.h)
-  GLX_UP(glx_zero_async(c->err + (size_t)std::min(c->min_iter, c->max_iter) * er, er * 8, c->stream));
+// 620 us step at config 2).  Invariant: the cleared row is zero before the sweep that does its atomic maxima into it -- stream order
+// behind the kernel that clears it; for min_iter = 0 row 0 then comes from the mirror, behind that kernel in the stream.
+// The stacked form (start_iterate = false) clears the row alone and resets its iterate itself (groups.hip).  The single form
+// (start_iterate = true) gets its whole reset from the one start kernel: buf[0] = (u = 0, stop value w0 through perm), the row
+// cleared by that kernel's first workgroup, cur = 0.
+int glx_sweep_head_rows(SweepCore* c, bool start_iterate) {
+  const size_t er = c->err_row(), rb = c->rec_bytes();
+  unsigned long long* row = c->err + (size_t)std::min(c->min_iter, c->max_iter) * er;
+  if (start_iterate) {
+    GLX_CHECK(c->B == 1 && c->L.woff >= 0 && c->L.woff % 16 == 0 && rb % 16 == 0 && c->L.woff + 8 <= (int)rb, GLX_EINVAL,
+              "sweep start: record of %zu bytes with its stop value at %d", rb, c->L.woff);
+    const int64_t npieces = c->n_cols * (int64_t)(rb / 16);
+    const unsigned grid = (unsigned)std::max<int64_t>(1, (npieces + 255) / 256);      // (an empty operator still clears its stop row)
+    hipLaunchKernelGGL(sweep_start_kernel, dim3(grid), dim3(256), 0, c->stream, (ulonglong2*)c->buf[0], npieces, (int)(rb / 16), c->L.woff / 16,
+                       (const double*)c->w0, (const int32_t*)c->P->d_perm, row, (int)er);
+    GLX_HIP(hipGetLastError());
+    c->cur = 0;
+  } else {
+    // (a kernel, not a memset node: this sequence is captured and replayed -- glx_zero_async, glx_internal.h)
+    GLX_UP(glx_zero_async(row, er * 8, c->stream));
+  }
   if (c->min_iter == 0) GLX_HIP(hipMemcpyAsync(c->err, c->h_err, er * 8, hipMemcpyHostToDevice, c->stream));
   return GLX_OK;
 }
@@ -214,15 +248,23 @@ int glx_sweep_head_rows(SweepCore* c) {
 // forward, a launch behind the last group's stop returns at once --, so over-launching is harmless and the host only reads the maxima
 // back: row t in front of a chunk, rows t + 1 .. end behind it (which of the chunk's sweeps really ran?).  Ends with the run
 // complete: c->walk finished, c->cur on the buffer that holds u_T.
+// A run that stops at its head (the usual one: min_iter sweeps suffice) costs ONE host wait: ev1 is recorded behind the read-back of
+// row `head`, and the wait for that row is the wait for the run.  A walk that goes on records ev1 again at its end.
 int glx_sweep_tail(SweepCore* c, const std::function<int(int)>& launch, float* device_ms_out) {
   StopWalk& w = c->walk;
   const size_t er = c->err_row();
   int t = w.head;
+  bool ended = false;      // ev1 stands behind everything enqueued, and the host has waited for it
   while (t < w.max_iter && w.running()) {
     GLX_HIP(hipMemcpyAsync(c->h_err + (size_t)t * er, c->err + (size_t)t * er, er * 8, hipMemcpyDeviceToHost, c->stream));
+    const bool at_head = t == w.head;
+    if (at_head) GLX_HIP(hipEventRecord(c->ev1, c->stream));
     GLX_HIP(hipStreamSynchronize(c->stream));
     w.test(t, c->h_err + (size_t)t * er, c->shards);
-    if (!w.running()) break;
+    if (!w.running()) {
+      ended = at_head;
+      break;
+    }
     const int end = w.chunk_end(t), t0 = t;
     // rows t0 + 1 .. end: what this chunk's sweeps write (atomic maxima: they must start from 0)
     GLX_HIP(hipMemsetAsync(c->err + (size_t)(t0 + 1) * er, 0, (size_t)(end - t0) * er * 8, c->stream));
@@ -233,8 +275,10 @@ int glx_sweep_tail(SweepCore* c, const std::function<int(int)>& launch, float* d
     for (int q = t0 + 1; q < end; ++q) w.test(q, c->h_err + (size_t)q * er, c->shards);   // (row `end` opens the next round)
   }
   c->cur = StopWalk::parity(w.finish());
-  GLX_HIP(hipEventRecord(c->ev1, c->stream));
-  GLX_HIP(hipStreamSynchronize(c->stream));
+  if (!ended) {
+    GLX_HIP(hipEventRecord(c->ev1, c->stream));
+    GLX_HIP(hipStreamSynchronize(c->stream));
+  }
   if (device_ms_out) GLX_HIP(hipEventElapsedTime(device_ms_out, c->ev0, c->ev1));
   return GLX_OK;
 }
