@@ -159,6 +159,8 @@ _SIGNATURES = {
     'glx_components_plan': [_i64p],
     'glx_boundary_stat': [C.c_int64, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _f64p, C.c_int],
     'glx_boundary_stat_set_wave_row': [C.c_int],
+    'glx_peikonal': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, C.c_int64, _vp, _i64p, _f64p,
+                     C.c_int],
     'glx_lip_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_double,
                         _vp, _vp, _vp, _vp, C.c_int, C.c_int],
     'glx_slp_iterate': [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int],
@@ -1204,6 +1206,35 @@ def boundary_stat(X, indptr, indices, second_order=True, cutoff=True, J=None, de
 def boundary_stat_set_wave_row(min_members=0):
     """plan override of the calling thread for measurements: rows of at least `min_members` members take a wavefront (0: the library's)"""
     call('glx_boundary_stat_set_wave_row', int(min_members))
+
+
+peikonal_last_ms = None         # host milliseconds of the last call: uploads, rounds, download
+
+
+def peikonal(row_ptr, nbr, W, f, bdy_ptr, bdy_idx, bdy_val, p, num_bisection_it, u0, device=None, max_rounds=0):
+    """The p-eikonal equation for B = len(bdy_ptr) - 1 boundary sets on one graph (glx_peikonal, csrc/peik.hip): the stored entries
+    sorted by vertex (row_ptr (n + 1), nbr, W), f (n), the boundary lists and their values, u0 (n) for vertices no boundary reaches.
+    Returns (u (n, B) float64, rounds).  max_rounds: 0, or a cap below the library's own (peik_round_cap of csrc/peik_plan.h; a test hook)."""
+    global peikonal_last_ms
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    u0 = np.ascontiguousarray(u0, dtype=np.float64)
+    bdy_ptr = np.ascontiguousarray(bdy_ptr, dtype=np.int64)
+    bdy_idx = np.ascontiguousarray(bdy_idx, dtype=np.int32)
+    bdy_val = np.ascontiguousarray(bdy_val, dtype=np.float64)
+    n, B = len(row_ptr) - 1, len(bdy_ptr) - 1
+    if (n < 1 or B < 1 or nbr.ndim != 1 or len(nbr) != len(W) or f.shape != (n,) or u0.shape != (n,) or bdy_idx.ndim != 1
+            or len(bdy_idx) != len(bdy_val) or len(bdy_idx) != bdy_ptr[-1]):
+        raise GlxError('peikonal: inconsistent array shapes')
+    u = np.empty((n, B), dtype=np.float64)
+    rounds = C.c_int64(0)
+    ms = (C.c_double * 3)(0, 0, 0)
+    call('glx_peikonal', n, len(nbr), _ptr(row_ptr), _ptr(nbr), _ptr(W), _ptr(f), B, _ptr(bdy_ptr), _ptr(bdy_idx), _ptr(bdy_val), float(p),
+         int(num_bisection_it), _ptr(u0), int(max_rounds), _ptr(u), C.byref(rounds), ms, _dev(device))
+    peikonal_last_ms = tuple(ms)
+    return u, int(rounds.value)
 
 
 def lip_iterate(n, nbr, row, W, ind, val, weighted, alpha, beta, T, tol, device=None, want_errors=False, small_level=-1):

@@ -371,6 +371,108 @@ class graph:
         self.amle_iters = int(self.amle_iters[0])
         return np.ascontiguousarray(u[:, 0])
 
+    def _peikonal_batch(self, bdy_sets, bdy_vals=0, f=1, p=1, u0=None, num_bisection_it=30, device=None, max_rounds=0):
+        """B p-eikonal problems on this graph in one device call (glx_peikonal): `bdy_sets` is a list of boundary sets (indices or
+        masks), `bdy_vals` one value (a float or an array per set) for all of them or a list with one per set.  Returns u (n, B)
+        float64; every column equals the single `peikonal` call bit for bit.  Sets peikonal_rounds.  Refused with ValueError before
+        any device call: the refusals of `peikonal`.  max_rounds: a cap on the rounds below the library's own (a test hook)."""
+        from . import _hip, utils
+        n = self.num_nodes
+        I, J, V = self._entries()
+        if not np.all(np.isfinite(V) & (V > 0)):
+            raise ValueError('graph.peikonal: the weight matrix has an entry that is not finite or not positive')
+        if type(f) != np.ndarray:           # the reference's `f = np.ones((n,))*f`
+            f = np.ones((n,)) * f
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape != (n,):
+            raise ValueError('graph.peikonal: f has shape %s, expected (%d,)' % (f.shape, n))
+        if not np.all(np.isfinite(f) & (f >= 0)):
+            raise ValueError('graph.peikonal: f has an entry that is negative or not finite')
+        u0 = np.zeros((n,)) if u0 is None else np.ascontiguousarray(u0, dtype=np.float64)
+        if u0.shape != (n,):
+            raise ValueError('graph.peikonal: u0 has shape %s, expected (%d,)' % (u0.shape, n))
+        if not np.all(np.isfinite(u0)):
+            raise ValueError('graph.peikonal: u0 has a non-finite entry')
+        p = float(p)
+        if not (np.isfinite(p) and p > 0):
+            raise ValueError('graph.peikonal: p=%r is not finite or not positive' % (p,))
+        nb = int(num_bisection_it)
+        if nb != num_bisection_it or not 1 <= nb <= 128:
+            raise ValueError('graph.peikonal: num_bisection_it=%r outside 1 .. 128' % (num_bisection_it,))
+        bdy_sets = list(bdy_sets)
+        B = len(bdy_sets)
+        if not 1 <= B <= 256:
+            raise ValueError('graph.peikonal: %d boundary sets in one call (1 .. 256 are supported)' % B)
+        if n * B > (1 << 31):
+            raise ValueError('graph.peikonal: n * B = %d values above the supported 2^31' % (n * B))
+        if not isinstance(bdy_vals, (list, tuple)):
+            bdy_vals = [bdy_vals] * B
+        if len(bdy_vals) != B:
+            raise ValueError('graph.peikonal: %d boundary value entries for %d boundary sets' % (len(bdy_vals), B))
+        ptr, idx, val = [0], [], []
+        for bdy_set, bdy_val in zip(bdy_sets, bdy_vals):
+            bdy_set = np.asarray(bdy_set)
+            m = int(np.sum(bdy_set)) if bdy_set.dtype == bool else bdy_set.size
+            if np.ndim(bdy_val) > 0 and np.size(bdy_val) != m:
+                raise ValueError('graph.peikonal: %d boundary values for %d boundary vertices' % (np.size(bdy_val), m))
+            bdy_set, bdy_val = utils._boundary_handling(bdy_set, bdy_val)
+            bdy_set = np.ascontiguousarray(bdy_set, dtype=np.int64).ravel()
+            bdy_val = np.ascontiguousarray(bdy_val, dtype=np.float64).ravel()
+            if len(bdy_set) == 0:
+                raise ValueError('graph.peikonal: an empty boundary set')
+            if bdy_set.min() < 0 or bdy_set.max() >= n:
+                raise ValueError('graph.peikonal: boundary index out of range')
+            if not np.all(np.isfinite(bdy_val)):
+                raise ValueError('graph.peikonal: bdy_val has a non-finite entry')
+            idx.append(bdy_set.astype(np.int32))
+            val.append(bdy_val)
+            ptr.append(ptr[-1] + len(bdy_set))
+        row_ptr = np.concatenate(([0], np.cumsum(np.bincount(I, minlength=n)))).astype(np.int64)
+        u, rounds = _hip.peikonal(row_ptr, J, V, f, np.array(ptr, dtype=np.int64), np.concatenate(idx), np.concatenate(val), p, nb, u0,
+                                  device=device, max_rounds=max_rounds)
+        self.peikonal_rounds = rounds
+        return u
+
+    def peikonal(self, bdy_set, bdy_val=0, f=1, p=1, nl_bdy=False, u0=None, solver='fmm', max_num_it=1e5, tol=1e-3, num_bisection_it=30,
+                 prog=False, device=None):
+        """The graph p-eikonal equation sum_j w_ij (u_i - u_j)_+^p = f_i off the boundary, u = bdy_val on it (reference
+        graph.py:793-914).  `solver='fmm'`, the reference's fast-marching pass peikonal_fmm_main, runs on the GPU as synchronous
+        fixed-point rounds with the same local solves (glx_peikonal; the argument heads csrc/peik_plan.h): for p = 1 the marching
+        solver's values bit for bit, for p != 1 to the resolution of the `num_bisection_it` halvings.  A vertex no boundary vertex
+        reaches keeps `u0` (0 by default), as in the reference.  `nl_bdy=True` extends the boundary to its graph neighbours by the
+        reference's host expressions.  Returns u float64 (n,); sets peikonal_rounds.  max_num_it, tol and prog belong to the
+        'gauss-seidel' solver, an in-order sweep that has an exact parallel form -- the level schedule of csrc/lip_plan.h -- but is not
+        switched on: NotImplementedError (for p = 1 it converges to the values 'fmm' returns).  Refused with ValueError before any
+        device call: `bdy_val` of another length than the boundary set, an empty boundary set, an index out of range, a weight that is
+        not finite and positive, an `f` that is negative or not finite, a non-finite `bdy_val` or `u0`, p not finite or <= 0,
+        num_bisection_it outside 1 .. 128."""
+        from . import utils
+        if solver != 'fmm':
+            if solver == 'gauss-seidel':
+                raise NotImplementedError("graph.peikonal(solver='gauss-seidel') is not switched on: the reference's in-order sweep is a "
+                                          "level schedule (csrc/lip_plan.h) that is not wired to this equation; use solver='fmm'")
+            raise ValueError("graph.peikonal: unknown solver %r ('fmm' or 'gauss-seidel')" % (solver,))
+        n = self.num_nodes
+        bdy_set = np.asarray(bdy_set)
+        m = int(np.sum(bdy_set)) if bdy_set.dtype == bool else bdy_set.size
+        if np.ndim(bdy_val) > 0 and np.size(bdy_val) != m:
+            raise ValueError('graph.peikonal: %d boundary values for %d boundary vertices' % (np.size(bdy_val), m))
+        bdy_set, bdy_val = utils._boundary_handling(bdy_set, bdy_val)
+        if nl_bdy:                           # reference graph.py:891-901, the same scipy expressions
+            if len(bdy_set) and (np.min(bdy_set) < 0 or np.max(bdy_set) >= n):
+                raise ValueError('graph.peikonal: boundary index out of range')
+            D = self.degree_matrix(p=-1)
+            bdy_mask = np.zeros(n)
+            bdy_mask[bdy_set] = 1
+            bdy_dilate = (D * self.weight_matrix * bdy_mask) > 0
+            bdy_set = np.where(bdy_dilate)[0]
+            bdy_val_all = np.zeros(n)
+            bdy_val_all[bdy_mask == 1] = bdy_val
+            bdy_val = D * self.weight_matrix * bdy_val_all
+            bdy_val = bdy_val[bdy_set]
+        u = self._peikonal_batch([bdy_set], [bdy_val], f=f, p=p, u0=u0, num_bisection_it=num_bisection_it, device=device)
+        return np.ascontiguousarray(u[:, 0])
+
     def neighbors(self, i, return_weights=False):
         """Neighbours of vertex i (and the weights of the edges to them), reference graph.py:124-151."""
         N = self.weight_matrix[i, :].nonzero()[1]

@@ -1286,6 +1286,51 @@ class amle(ssl):
         return u
 
 
+class peikonal(ssl):
+    def __init__(self, W=None, class_priors=None, D=None, p=1, alpha=1, max_num_it=1e5, tol=1e-3, num_bisection_it=30, eps_ball_graph=False):
+        """Graph p-eikonal classifier (reference ssl.py:1616-1678): one-vs-rest, class l's score is graph.peikonal with the class's
+        labelled vertices as the boundary at value 0 -- a distance, so the smallest score wins (`similarity = False`).  D: (n, n)
+        sparse matrix of neighbour distances, reweights the equation by f = (distance to the farthest neighbour / its maximum)**alpha;
+        `eps_ball_graph=True` (without D) takes the degree vector as the density estimate, f = (d / max d)**(-alpha).  max_num_it and
+        tol are kept for the reference's signature (they belong to its Gauss-Seidel solver, which the learner never uses).  All
+        classes are solved as the columns of one device call (graph._peikonal_batch); num_iter: its rounds."""
+        super().__init__(W, class_priors)
+        self.p = p
+        self.alpha = alpha
+        self.max_num_it = max_num_it
+        self.tol = tol
+        self.num_bisection_it = num_bisection_it
+        self.onevsrest = True
+        self.similarity = False
+        if not (np.isfinite(float(p)) and float(p) > 0):
+            raise ValueError('ssl.peikonal: p=%r is not finite or not positive' % (p,))
+        if int(num_bisection_it) != num_bisection_it or not 1 <= int(num_bisection_it) <= 128:
+            raise ValueError('ssl.peikonal: num_bisection_it=%r outside 1 .. 128' % (num_bisection_it,))
+        if D is None:
+            if eps_ball_graph:
+                d = self.graph.degree_vector()
+                self.f = (d / np.max(d)) ** (-alpha)
+            else:
+                self.f = 1
+        else:
+            d = D.max(axis=1).toarray().flatten()
+            self.f = (d / np.max(d)) ** alpha
+        self.accuracy_filename = '_peikonal_p%.2f_alpha%.2f' % (self.p, self.alpha)
+        self.name = 'p-eikonal (p=%.2f, alpha=%.2f)' % (self.p, self.alpha)
+
+    def _fit(self, train_ind, train_labels, all_labels=None):
+        u = self.graph.peikonal(train_ind[train_labels], bdy_val=0, f=self.f, p=self.p, max_num_it=self.max_num_it, tol=self.tol,
+                                num_bisection_it=self.num_bisection_it, prog=False, device=self.device)
+        self.num_iter = self.graph.peikonal_rounds
+        return u
+
+    def _fit_onevsrest(self, train_ind, train_labels, unique_labels):
+        u = self.graph._peikonal_batch([train_ind[train_labels == l] for l in unique_labels], 0, f=self.f, p=self.p,
+                                       num_bisection_it=self.num_bisection_it, device=self.device)
+        self.num_iter = self.graph.peikonal_rounds
+        return u
+
+
 class plaplace(ssl):
     def __init__(self, W=None, class_priors=None, p=10, max_num_it=1e6, tol=1e-1, fast=True):
         """Semi-supervised learning by the game-theoretic p-Laplace equation (reference ssl.py:1681-1727; Flores Rios, Calder and

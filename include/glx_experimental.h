@@ -441,6 +441,26 @@ int glx_boundary_stat(int64_t n, int d, const double* X, int64_t nnz, const int3
                       const int32_t* J, int flags, double* T, double* nu, double* stats_out, int device);
 int glx_boundary_stat_set_wave_row(int min_members);
 
+/* ---- p-eikonal equation: graph.peikonal / ssl.peikonal (csrc/peik.hip, csrc/peik_plan.h) --------------------------------------------
+ * sum_j w_ij (u_i - u_j)_+^p = f_i off the boundary, u = g on it: peikonal_fmm_main of the reference's C extension
+ * (c_code/hjsolvers.cpp:342-420) as synchronous fixed-point rounds u_j <- min(u_j, S_j(u)) from +inf, neighbours at +inf left out;
+ * the arithmetic, operation by operation, heads csrc/peik_plan.h.  For p == 1 the result equals peik_host_reference (and the
+ * reference's marching solver) bit for bit; for p != 1 the local solve is num_bisection_it halvings with the device's pow.
+ * The graph arrives as the reference hands it over: M stored entries sorted by vertex, row_ptr (n + 1) their blocks, nbr the
+ * neighbour, W the weight (finite, > 0); a stored self loop is skipped.  f (n) >= 0.  B problems on that graph: problem b's boundary
+ * vertices are bdy_idx[bdy_ptr[b] .. bdy_ptr[b + 1]) with the values bdy_val (a vertex listed twice takes its last value; a list may
+ * not be empty).  u0 (n): the value of a vertex no boundary reaches.  max_rounds: 0, or a cap below the library's (2 n + 2 rounds,
+ * and 8 more per halving for p != 1: csrc/peik_plan.h; a test hook).
+ * u (n, B) row-major: the result.  *rounds_out (or NULL): the rounds run, the idle last one included.  ms_out[3] (or NULL): host
+ * milliseconds of the uploads, the rounds and the download.  One launch per round, the flags of 32 rounds read at once; no result
+ * depends on that length.  All pointers are host pointers.
+ * GLX_EINVAL: a null argument, bad sizes or row pointers, an index out of range, an empty boundary list, a weight that is not finite
+ * and > 0, an f that is negative or not finite, a g or u0 that is not finite, p not finite or <= 0, num_bisection_it outside 1 .. 128.
+ * GLX_EUNSUPPORTED: B outside 1 .. 256, n * B > 2^31, or values that still fall after the cap on the rounds. */
+int glx_peikonal(int64_t n, int64_t M, const int64_t* row_ptr, const int32_t* nbr, const double* W, const double* f, int B,
+                 const int64_t* bdy_ptr, const int32_t* bdy_idx, const double* bdy_val, double p, int num_bisection_it, const double* u0,
+                 int64_t max_rounds, double* u, int64_t* rounds_out, double* ms_out, int device);
+
 #ifdef __cplusplus
 }
 #endif
